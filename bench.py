@@ -18,6 +18,9 @@ RANK / LOCAL_RANK / WORLD_SIZE as given.  Besides the kernel-only headline value
 Inputs are synthetic (rust_compress_amd.synth) and are compressed on the GPU by the product's own bit-exact LZ4 encoder;
 the oracle is used only for the cpu_baseline leg (and its parity check).
 
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs): the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
+
 `--dry-gloo` (CPU test of the launcher / rank / scatter / gather logic only): gloo backend, CPU tensors, a tiny workload,
 and the block codec taken from the module named by RCX_BENCH_DRY_CODEC (the test suite supplies it; this file never
 imports the oracle outside cpu_baseline).
@@ -32,6 +35,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -41,6 +45,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 BLOCK = 65536
 NBLOCKS = 4096
+DUMP_SAMPLE_BLOCKS = 128       # --dump-outputs: decoded bytes of this many blocks (as float32: 32 MiB of the 64 MB a dump may hold)
 HEADLINE_KERNEL_SOURCES = ["k_lz4_decode_v4.hip", "k_lz4_decode_v5.hip", "k_lz4_emit6.hip", "k_lz4_decode_v8.hip", "rcx_dev.h"]
 
 
@@ -100,6 +105,12 @@ class GpuEngine:
 
     def events(self, n):
         return [self.torch.cuda.Event(enable_timing=True) for _ in range(n)]
+
+    def outputs(self, wl):
+        """what the last decode handed its caller, on the host: (nblocks x BLOCK bytes, decoded lengths, statuses)"""
+        dec, nb = wl["dec"], wl["nblocks"]
+        self.sync()
+        return (dec.out_base[: nb * BLOCK].cpu().numpy().reshape(nb, BLOCK), dec.out_len[:nb].cpu().numpy(), dec.status[:nb].cpu().numpy())
 
     def compressed(self, wl):
         dec = wl["dec"]
@@ -185,6 +196,12 @@ class DryEngine:
             def elapsed_time(s, o): return (o.t - s.t) * 1e3
         return [Ev() for _ in range(n)]
 
+    def outputs(self, wl):
+        out = np.zeros((wl["nblocks"], BLOCK), dtype=np.uint8)
+        for i, b in enumerate(wl["out"]):
+            out[i, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+        return out, np.array([len(b) for b in wl["out"]], dtype=np.int64), np.zeros(wl["nblocks"], dtype=np.int32)
+
     def compressed(self, wl):
         return wl["base"], wl["off"], wl["lens"]
 
@@ -253,6 +270,21 @@ def time_steps(eng, wl, steps, warmup, dist):
     wall = time.perf_counter() - t0
     kern_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(steps)]
     return wall, float(np.mean(kern_ms)), float(np.median(kern_ms))
+
+
+def dump_outputs(eng, wl, path):
+    """--dump-outputs DIR: what the timed path returned in its last step, as float arrays that a dump of another build (same
+    arguments, so the same inputs) can be compared with element for element: every block's status, decoded length and CRC-32
+    over its whole output slot, and the decoded bytes of a fixed, seeded sample of the blocks."""
+    out, out_len, status = eng.outputs(wl)
+    nb = wl["nblocks"]
+    idx = np.sort(np.random.default_rng(0x5EED0D).choice(nb, size=min(nb, DUMP_SAMPLE_BLOCKS), replace=False))
+    arrays = {"block_status": status.astype(np.float64), "block_out_len": out_len.astype(np.float64),
+              "block_crc32": np.array([zlib.crc32(out[i]) for i in range(nb)], dtype=np.float64),
+              "sample_block_index": idx.astype(np.float64), "sample_decoded_bytes": out[idx].astype(np.float32)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(dec, raw, torch, nblocks, budget_s=10.0):
@@ -657,6 +689,7 @@ def main():
     ap.add_argument("--others-scale", type=float, default=1.0, help="fraction of the full size of configs 3-5")
     ap.add_argument("--extras", action="store_true", help="also time the other distributions / variants")
     ap.add_argument("--dry-gloo", action="store_true", help="CPU test of the multi-rank plumbing (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -707,6 +740,8 @@ def main():
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
     wall = float(t.item())
     total_out = float(tot[0].item())
+    if args.dump_outputs and rank == 0:                         # (untimed, and before any side leg launches the decoder again)
+        dump_outputs(eng, wl, args.dump_outputs)
 
     # ---- the headline is complete here.  Rank 0 stashes the line now; everything below is a SIDE LEG that runs under
     # SideLegs.run (every rank catches, one all_reduce(MAX) of an error flag decides together whether the ranks can go on

@@ -1,10 +1,13 @@
 """CPU suite: `bench.py --gpus N` really starts N ranks and its end-to-end leg (root scatter -> decode -> root gather)
 moves the right bytes.  Runs the benchmark's own code on gloo with the oracle as the block codec (--dry-gloo)."""
+import importlib
 import json
 import os
 import subprocess
 import sys
+import zlib
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,3 +102,31 @@ def test_container_split_join(oracle):
         P.parse_container(whole[:40])
     with pytest.raises(P.ContainerError):
         P.join_containers([whole, D.pipe_encode(data[:100], 1024)])
+
+
+def test_bench_dump_outputs_is_the_last_steps_result_and_repeats(oracle, tmp_path):
+    """--dump-outputs DIR: float arrays of what the timed decode returned, within 64 MB, the same from run to run; --steps is
+    the number of timed steps and the line carries ms_per_step."""
+    env = dict(os.environ, RCX_BENCH_DRY_CODEC="_dry_codec", PYTHONPATH=os.path.join(ROOT, "tests") + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("dump%d" % run)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-gloo", "--nblocks", "3", "--steps", "3", "--warmup", "1",
+                            "--no-e2e", "--no-others", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+        res = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        files = sorted(os.listdir(d))
+        assert files == ["block_crc32.npy", "block_out_len.npy", "block_status.npy", "sample_block_index.npy", "sample_decoded_bytes.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f[:-4]: np.load(d / f) for f in files})
+    a, b = dumps
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert (a["block_status"] == 0).all() and (a["block_out_len"] == 65536).all() and a["sample_block_index"].tolist() == [0, 1, 2]
+    raw = a["sample_decoded_bytes"].astype(np.uint8)
+    assert [zlib.crc32(r.tobytes()) for r in raw] == a["block_crc32"].astype(np.int64).tolist()
+    _, raws = importlib.import_module("_dry_codec").make_blocks("text", 3, 65536, 0x4C5A3401)
+    assert [r.tobytes() for r in raw] == raws
