@@ -161,6 +161,20 @@ int rcx_crc32_batch(rcx_ctx*, const rcx_batch*, uint32_t* crc);
 /* one gzip member per block: header (FEXTRA/FNAME/FCOMMENT/FHCRC skipped), DEFLATE stream decoded to BFINAL,
  * CRC32 + ISIZE trailer verified; in_used[i] = bytes of the member.  flags as rcx_inflate_batch. */
 int rcx_gzip_decode_batch(rcx_ctx*, const rcx_batch*, uint32_t* flags);
+/* ---- extension beyond the reference (it has no DEFLATE encoder) ----
+ * One input block -> one complete raw DEFLATE stream (RFC 1951), zlib stream (RFC 1950: 78 01, Adler-32 big-endian) or gzip member
+ * (RFC 1952: 10-byte header, no optional fields, MTIME 0, OS 255; CRC-32 and ISIZE little-endian).  Greedy LZ77 over a 32 KiB window
+ * (also across the encoder's internal 64 KiB segments), one block per segment, each the cheapest of stored, fixed and dynamic Huffman;
+ * no block decodes to zero bytes except the lone final block of an empty input.  The output is deterministic: the same bytes for the
+ * same input at any position of any batch.  On success out_len[i] = bytes written, in_used[i] = in_len[i].  A slot smaller than the
+ * stream gets RCX_E_OUTPUT_TOO_SMALL (out_len 0) and nothing of it is written.  rcx_launch_dev needs
+ * rcx_scratch_bytes(codec, nblocks, max_block) of scratch: too little and the streams it does not cover get RCX_E_MALFORMED.
+ * A block may be up to 2^32 - 1 bytes; a longer one gets RCX_E_MALFORMED through rcx_launch_dev (the batch calls refuse it). */
+int rcx_deflate_encode_batch(rcx_ctx*, const rcx_batch*);
+int rcx_zlib_encode_batch(rcx_ctx*, const rcx_batch*);
+int rcx_gzip_encode_batch(rcx_ctx*, const rcx_batch*);
+/* largest raw DEFLATE stream of n input bytes; a zlib stream needs 6 bytes more, a gzip member 18 */
+uint64_t rcx_deflate_compression_bound(uint64_t n);
 
 /* ---- BWT / MTF / DC --------------------------------------------------------- */
 /* reference: src/bwt/mod.rs:136-219 compute_suffixes + TransformIterator.
@@ -265,10 +279,11 @@ enum rcx_codec {
     RCX_RLE_ENCODE, RCX_RLE_DECODE, RCX_CRC32, RCX_GZIP_DECODE,
     RCX_ARI_BINARY_ENCODE, RCX_ARI_BINARY_DECODE, RCX_ARI_PROXY_ENCODE, RCX_ARI_PROXY_DECODE,
     RCX_ARI_APM_ENCODE, RCX_ARI_APM_DECODE, RCX_BWT_INVERSE_MINIMAL,
-    RCX_BWT_SUFFIXES, RCX_BWT_INVERSION_TABLE, RCX_CODEC_COUNT
+    RCX_BWT_SUFFIXES, RCX_BWT_INVERSION_TABLE,
+    RCX_DEFLATE_ENCODE, RCX_ZLIB_ENCODE, RCX_GZIP_ENCODE, RCX_CODEC_COUNT
 };
 /* scratch bytes (HBM) the codec needs for nblocks blocks of <= max_block bytes.  Required for LZ4 encode, BWT and gzip
- * decode; for RCX_INFLATE / RCX_ZLIB_DECODE it is what the default (wave-per-stream) decoder needs -- without it
+ * decode and the DEFLATE / zlib / gzip encoders; for RCX_INFLATE / RCX_ZLIB_DECODE it is what the default (wave-per-stream) decoder needs -- without it
  * rcx_launch_dev falls back to the lane-per-stream kernel (same results, slower on small batches). */
 uint64_t rcx_scratch_bytes(int codec, uint32_t nblocks, uint64_t max_block);
 int rcx_launch_dev(rcx_ctx*, int codec, const rcx_dev_batch*, void* scratch, uint64_t scratch_bytes);

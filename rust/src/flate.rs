@@ -1,8 +1,8 @@
 //! RFC 1951 decoder (reference: src/flate.rs:164-193, 453-488).  Batch semantics: the stream is decoded to BFINAL in one
 //! call; `flags & RCX_W_EMPTY_BLOCK_MIDSTREAM` reports the reference's `Ok(0)` quirk (:474-476) instead of acting it out.
 use crate::rcx_sys::*;
-use crate::{decode_many_with, grow_decode, Buffered, TailReader};
-use std::io::{self, Read};
+use crate::{decode_many_with, grow_decode, run_batch, Buffered, TailReader};
+use std::io::{self, Read, Write};
 
 pub struct Decoder<R: Read> {
     /// `pub r: R` (flate.rs:166), left exactly after the DEFLATE stream once it is decoded (:250-260 reads byte by byte)
@@ -42,4 +42,36 @@ impl<R: Read> Read for Decoder<R> {
 /// bytes used, flags); the first stream that fails returns what its `Decoder` would.
 pub fn decode_many(streams: &[&[u8]]) -> io::Result<Vec<(Vec<u8>, usize, u32)>> {
     decode_many_with(streams, |c, b, f| unsafe { rcx_inflate_batch(c, b, f) })
+}
+
+/// Extension (the reference has no DEFLATE encoder): the whole input as ONE stream.  `write` only buffers -- there is no incremental
+/// state across calls -- and `finish` encodes everything in one batch call, writes it to `w` and returns the writer.
+pub struct Encoder<W: Write> {
+    w: W,
+    buf: Vec<u8>,
+}
+
+impl<W: Write> Encoder<W> {
+    pub fn new(w: W) -> Encoder<W> {
+        Encoder { w, buf: Vec::new() }
+    }
+    pub fn finish(mut self) -> (W, io::Result<()>) {
+        let cap = unsafe { rcx_deflate_compression_bound(self.buf.len() as u64) };
+        let r = run_batch(&[&self.buf[..]], &[cap], |c, b, _| unsafe { rcx_deflate_encode_batch(c, b) }).check();
+        let res = match r {
+            Ok(r) => self.w.write_all(&r.out[0]),
+            Err(e) => Err(e),
+        };
+        (self.w, res)
+    }
+}
+
+impl<W: Write> Write for Encoder<W> {
+    fn write(&mut self, buf: &[u8]) -> io::Result<usize> {
+        self.buf.extend_from_slice(buf);
+        Ok(buf.len())
+    }
+    fn flush(&mut self) -> io::Result<()> {
+        Ok(())
+    }
 }

@@ -111,7 +111,10 @@ pub const RCX_ARI_APM_DECODE: c_int = 22;
 pub const RCX_BWT_INVERSE_MINIMAL: c_int = 23;
 pub const RCX_BWT_SUFFIXES: c_int = 24;
 pub const RCX_BWT_INVERSION_TABLE: c_int = 25;
-pub const RCX_CODEC_COUNT: c_int = 26;
+pub const RCX_DEFLATE_ENCODE: c_int = 26;
+pub const RCX_ZLIB_ENCODE: c_int = 27;
+pub const RCX_GZIP_ENCODE: c_int = 28;
+pub const RCX_CODEC_COUNT: c_int = 29;
 
 #[link(name = "rcx")]
 extern "C" {
@@ -132,6 +135,11 @@ extern "C" {
     pub fn rcx_adler32_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, adler: *mut u32) -> c_int;
     pub fn rcx_crc32_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, crc: *mut u32) -> c_int;
     pub fn rcx_gzip_decode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32) -> c_int;
+    // ---- the DEFLATE / zlib / gzip encoders (extension: the reference has no DEFLATE encoder)
+    pub fn rcx_deflate_encode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch) -> c_int;
+    pub fn rcx_zlib_encode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch) -> c_int;
+    pub fn rcx_gzip_encode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch) -> c_int;
+    pub fn rcx_deflate_compression_bound(n: u64) -> u64;
     // ---- BWT / MTF / DC (src/bwt/mod.rs, mtf.rs, dc.rs)
     pub fn rcx_bwt_forward_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;
     pub fn rcx_bwt_suffixes_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;

@@ -1,7 +1,7 @@
 //! RFC 1950 decoder (reference: src/zlib.rs:32-127): CMF/FLG checks, DEFLATE, Adler-32 trailer -- all on the device.
 use crate::rcx_sys::*;
-use crate::{decode_many_with, grow_decode, Buffered, TailReader};
-use std::io::{self, Read};
+use crate::{decode_many_with, grow_decode, run_batch, Buffered, TailReader};
+use std::io::{self, Read, Write};
 
 pub struct Decoder<R: Read> {
     r: TailReader<R>,
@@ -33,4 +33,36 @@ impl<R: Read> Read for Decoder<R> {
 /// bytes used); the first member that fails returns what its `Decoder` would.
 pub fn decode_many(members: &[&[u8]]) -> io::Result<Vec<(Vec<u8>, usize)>> {
     Ok(decode_many_with(members, |c, b, f| unsafe { rcx_zlib_decode_batch(c, b, f) })?.into_iter().map(|(o, u, _)| (o, u)).collect())
+}
+
+/// Extension (the reference has no DEFLATE encoder): the whole input as ONE stream.  `write` only buffers -- there is no incremental
+/// state across calls -- and `finish` encodes everything in one batch call, writes it to `w` and returns the writer.
+pub struct Encoder<W: Write> {
+    w: W,
+    buf: Vec<u8>,
+}
+
+impl<W: Write> Encoder<W> {
+    pub fn new(w: W) -> Encoder<W> {
+        Encoder { w, buf: Vec::new() }
+    }
+    pub fn finish(mut self) -> (W, io::Result<()>) {
+        let cap = unsafe { rcx_deflate_compression_bound(self.buf.len() as u64) } + 6;
+        let r = run_batch(&[&self.buf[..]], &[cap], |c, b, _| unsafe { rcx_zlib_encode_batch(c, b) }).check();
+        let res = match r {
+            Ok(r) => self.w.write_all(&r.out[0]),
+            Err(e) => Err(e),
+        };
+        (self.w, res)
+    }
+}
+
+impl<W: Write> Write for Encoder<W> {
+    fn write(&mut self, buf: &[u8]) -> io::Result<usize> {
+        self.buf.extend_from_slice(buf);
+        Ok(buf.len())
+    }
+    fn flush(&mut self) -> io::Result<()> {
+        Ok(())
+    }
 }

@@ -20,7 +20,7 @@ INFLATE_VARIANTS = (0, 9, 10, 11, 1) if AB else (0, 9, 10, 11)
 (LZ4_DECODE, LZ4_ENCODE, INFLATE, ZLIB_DECODE, ADLER32, BWT_FORWARD, BWT_INVERSE, MTF_ENCODE, MTF_DECODE,
  DC_ENCODE, DC_DECODE, ARI_BYTE_ENCODE, ARI_BYTE_DECODE, RLE_ENCODE, RLE_DECODE, CRC32, GZIP_DECODE,
  ARI_BINARY_ENCODE, ARI_BINARY_DECODE, ARI_PROXY_ENCODE, ARI_PROXY_DECODE, ARI_APM_ENCODE, ARI_APM_DECODE,
- BWT_INVERSE_MINIMAL, BWT_SUFFIXES, BWT_INVERSION_TABLE, CODEC_COUNT) = range(27)
+ BWT_INVERSE_MINIMAL, BWT_SUFFIXES, BWT_INVERSION_TABLE, DEFLATE_ENCODE, ZLIB_ENCODE, GZIP_ENCODE, CODEC_COUNT) = range(30)
 MEM_HOST, MEM_DEVICE = 0, 1
 # enum rcx_status (the ones Python code names; include/rcx.h has them all)
 E_EOF, E_OUTPUT_TOO_SMALL, E_MALFORMED = 1, 2, 3
@@ -41,6 +41,7 @@ EXPORTS = [
     "rcx_multi_create", "rcx_multi_destroy", "rcx_multi_count", "rcx_multi_ctx", "rcx_partition", "rcx_multi_batch",
     "rcx_multi_launch_dev", "rcx_multi_sync", "rcx_multi_last_error", "rcx_host_register", "rcx_host_unregister",
     "rcx_hbm_copy_probe", "rcx_multi_scatter_dev", "rcx_multi_gather_dev", "rcx_multi_transport",
+    "rcx_deflate_encode_batch", "rcx_zlib_encode_batch", "rcx_gzip_encode_batch", "rcx_deflate_compression_bound",
 ]
 
 
@@ -86,7 +87,7 @@ def lib():
         L.rcx_last_error.restype = C.c_char_p
         L.rcx_status_string.argtypes = [C.c_int]
         L.rcx_status_string.restype = C.c_char_p
-        for name in ("rcx_lz4_compression_bound", "rcx_ari_byte_encode_bound", "rcx_rle_encode_bound"):
+        for name in ("rcx_lz4_compression_bound", "rcx_ari_byte_encode_bound", "rcx_rle_encode_bound", "rcx_deflate_compression_bound"):
             f = getattr(L, name)
             f.argtypes = [C.c_uint64]
             f.restype = C.c_uint64
@@ -96,7 +97,8 @@ def lib():
         for name in ("rcx_lz4_decode_batch", "rcx_lz4_encode_batch", "rcx_mtf_encode_batch", "rcx_mtf_decode_batch",
                      "rcx_dc_encode_batch", "rcx_dc_encode_ctx_batch", "rcx_ari_byte_encode_batch", "rcx_ari_byte_decode_batch",
                      "rcx_rle_encode_batch", "rcx_rle_decode_batch", "rcx_ari_proxy_encode_batch", "rcx_ari_proxy_decode_batch",
-                     "rcx_ari_apm_encode_batch", "rcx_ari_apm_decode_batch"):
+                     "rcx_ari_apm_encode_batch", "rcx_ari_apm_decode_batch",
+                     "rcx_deflate_encode_batch", "rcx_zlib_encode_batch", "rcx_gzip_encode_batch"):
             getattr(L, name).argtypes = [C.c_void_p, C.POINTER(Batch)]
         for name in ("rcx_ari_binary_encode_batch", "rcx_ari_binary_decode_batch"):
             getattr(L, name).argtypes = [C.c_void_p, C.POINTER(Batch), C.c_uint32]

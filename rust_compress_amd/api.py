@@ -8,6 +8,11 @@ from . import _native as N
 from . import batch as B
 
 
+def deflate_bound(n):
+    """rcx_deflate_compression_bound(n): the largest raw DEFLATE stream the encoder makes from n bytes (zlib +6, gzip +18)."""
+    return int(N.lib().rcx_deflate_compression_bound(n))
+
+
 class RcxError(RuntimeError):
     pass
 
@@ -118,6 +123,19 @@ class Context:
     def gzip_decode(self, blobs, caps):
         """One gzip member (RFC 1952) per blob: header, DEFLATE, CRC32 + ISIZE (extension)."""
         return self._run_host("rcx_gzip_decode_batch", blobs, caps, extra_out=True)
+
+    def deflate_encode(self, blobs, caps=None):
+        """One raw DEFLATE stream (RFC 1951) per blob (extension: the reference has no DEFLATE encoder).  caps default to
+        rcx_deflate_compression_bound."""
+        return self._run_host("rcx_deflate_encode_batch", blobs, caps if caps is not None else [deflate_bound(len(b)) for b in blobs])
+
+    def zlib_encode(self, blobs, caps=None):
+        """One zlib stream (RFC 1950: 78 01, DEFLATE, Adler-32) per blob; caps default to the DEFLATE bound + 6."""
+        return self._run_host("rcx_zlib_encode_batch", blobs, caps if caps is not None else [deflate_bound(len(b)) + 6 for b in blobs])
+
+    def gzip_encode(self, blobs, caps=None):
+        """One gzip member (RFC 1952, no optional header fields, MTIME 0, OS 255) per blob; caps default to the DEFLATE bound + 18."""
+        return self._run_host("rcx_gzip_encode_batch", blobs, caps if caps is not None else [deflate_bound(len(b)) + 18 for b in blobs])
 
     def bwt_forward(self, blobs):
         return self._run_host("rcx_bwt_forward_batch", blobs, [len(b) for b in blobs], extra_out=True)

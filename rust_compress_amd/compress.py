@@ -4,6 +4,7 @@ like the reference's own tests:
 
     compress::lz4::{Decoder, Encoder, decode_block, encode_block, compression_bound}   src/lz4.rs
     compress::flate::Decoder, compress::zlib::Decoder                                 src/flate.rs, src/zlib.rs
+    flate / zlib / gzip .Encoder, .encode_many (extension: the reference has no DEFLATE encoder)
     compress::bwt::{Encoder, Decoder, encode_simple, decode_simple}                   src/bwt/mod.rs
     compress::bwt::mtf::{Encoder, Decoder}, compress::bwt::dc::{encode_simple, decode_simple}
     compress::entropy::ari::{ByteEncoder, ByteDecoder}                                src/entropy/ari/table.rs
@@ -361,6 +362,34 @@ class lz4:
 
 
 # ------------------------------------------------------------------------------------------------ flate / zlib
+class _OneShotEncoder:
+    """DEFLATE / zlib / gzip Encoder (extension: the reference has no DEFLATE encoder).  Shaped like lz4.Encoder, but it HOLDS its input:
+    write() only buffers, there is no incremental state across write() calls, and finish() encodes everything as ONE stream in one
+    batch call, writes it to the writer and returns the writer."""
+    _call = None
+
+    def __init__(self, w):
+        self.w = w
+        self.buf = bytearray()
+
+    def write(self, buf):
+        self.buf += bytes(buf)
+        return len(buf)
+
+    def flush(self):
+        pass
+
+    def finish(self):
+        res = _check(getattr(context(), self._call)([bytes(self.buf)]))
+        self.buf = bytearray()
+        self.w.write(res.outputs[0])
+        return self.w
+
+    @classmethod
+    def _encode_many(cls, blobs):
+        return _check(getattr(context(), cls._call)([bytes(b) for b in blobs])).outputs
+
+
 class flate:
     class Decoder(_BufferedDecoder):                   # flate.rs:164-488; batch semantics: decoded to BFINAL
         def _decode_all(self, data):
@@ -375,6 +404,14 @@ class flate:
         one stream is one wave's work here -- hand over many)."""
         return _decode_many(flate.Decoder, readers, lambda raws, caps: context().inflate(raws, caps), lambda x: max(1 << 16, 4 * len(x)))
 
+    class Encoder(_OneShotEncoder):                    # extension: one raw DEFLATE stream (RFC 1951) at finish()
+        _call = "deflate_encode"
+
+    @staticmethod
+    def encode_many(blobs):
+        """-> [bytes], one raw DEFLATE stream per input, all encoded by ONE batch call"""
+        return flate.Encoder._encode_many(blobs)
+
 
 class zlib:
     class Decoder(_BufferedDecoder):                   # zlib.rs:32-127
@@ -387,6 +424,14 @@ class zlib:
     def decode_many(readers):
         """-> [zlib.Decoder], every member decoded (and its Adler-32 checked) by ONE batch call"""
         return _decode_many(zlib.Decoder, readers, lambda raws, caps: context().zlib_decode(raws, caps), lambda x: max(1 << 16, 4 * len(x)))
+
+    class Encoder(_OneShotEncoder):                    # extension: one zlib stream (RFC 1950) at finish()
+        _call = "zlib_encode"
+
+    @staticmethod
+    def encode_many(blobs):
+        """-> [bytes], one zlib stream per input, all encoded by ONE batch call"""
+        return zlib.Encoder._encode_many(blobs)
 
 
 class gzip:
@@ -418,6 +463,14 @@ class gzip:
                 self.members += 1
             self.consumed = pos
             return b"".join(out)
+
+    class Encoder(_OneShotEncoder):                    # one gzip member (RFC 1952) at finish()
+        _call = "gzip_encode"
+
+    @staticmethod
+    def encode_many(blobs):
+        """-> [bytes], one gzip member per input, all encoded by ONE batch call"""
+        return gzip.Encoder._encode_many(blobs)
 
 
 class Crc32:                                           # extension, mirrors Adler32 below

@@ -10,6 +10,7 @@
 //     crc(A || B) = crc(A) * x^(8|B|) mod P  xor  crc(B)
 // (the pre/post conditioning cancels, as in zlib's crc32_combine).  All right-hand parts of one level have the same
 // length, so the level's multiplier is the square of the previous one: one x^(8 per) by square-and-multiply per block.
+#pragma once
 #include "rcx_dev.h"
 
 #define RCX_CRC_POLY 0xEDB88320u

@@ -144,6 +144,8 @@ extern "C" const char* rcx_status_string(int s)
 extern "C" uint64_t rcx_lz4_compression_bound(uint64_t n) { return n > 0x7e000000ull ? 0 : n + n / 255 + 16 + 4; }
 extern "C" uint64_t rcx_ari_byte_encode_bound(uint64_t n) { return 2 * n + 16; }
 extern "C" uint64_t rcx_rle_encode_bound(uint64_t n) { return n + n / 2 + 16; }
+// a 64 KiB segment is at worst two stored blocks: 2 x (3 header bits + 7 padding + 32 LEN/NLEN) = 84 bits <= 11 bytes; empty input: 2 bytes
+extern "C" uint64_t rcx_deflate_compression_bound(uint64_t n) { return n + 11 * rcx_tu_deflate_encode_segments(n) + 2; }
 
 // ---- scratch requirements ---------------------------------------------------------------------
 extern "C" uint64_t rcx_scratch_bytes(int codec, uint32_t nblocks, uint64_t max_block)
@@ -156,6 +158,10 @@ extern "C" uint64_t rcx_scratch_bytes(int codec, uint32_t nblocks, uint64_t max_
     case RCX_BWT_INVERSE: case RCX_BWT_INVERSE_MINIMAL: return rcx_tu_bwt_inverse_scratch(nblocks, max_block);
     case RCX_INFLATE: case RCX_ZLIB_DECODE: return rcx_tu_inflate_scratch(nblocks);
     case RCX_GZIP_DECODE: return rcx_tu_gzip_scratch(nblocks) + rcx_tu_inflate_scratch(nblocks) + 512;   // + the carve's alignment slack
+    // every block counted at max_block: the per-segment staging of nblocks * segments(max_block) segments (the host batch path sizes it
+    // from the real lengths instead)
+    case RCX_DEFLATE_ENCODE: case RCX_ZLIB_ENCODE: case RCX_GZIP_ENCODE:
+        return rcx_tu_deflate_encode_scratch(nblocks, (uint64_t)nblocks * rcx_tu_deflate_encode_segments(max_block));
     default: return 0;
     }
 }
@@ -191,6 +197,10 @@ static int launch_codec(rcx_ctx* c, int codec, rcx_kargs& k, int param_over = -1
         if (k.scratch_bytes < rcx_tu_gzip_scratch(n)) { c->err = "gzip decode: scratch too small"; return RCX_RC_BAD_ARG; }
         rcx_tu_gzip_decode(s, k, v);
         break;
+    case RCX_DEFLATE_ENCODE: case RCX_ZLIB_ENCODE: case RCX_GZIP_ENCODE: {
+        int rc = rcx_tu_deflate_encode(s, k, codec == RCX_DEFLATE_ENCODE ? 0 : codec == RCX_ZLIB_ENCODE ? 1 : 2, c->err);
+        if (rc) return rc;
+        break; }
     case RCX_BWT_FORWARD: case RCX_BWT_SUFFIXES: {
         int rc = rcx_tu_bwt_forward(s, k, v, c->err, codec == RCX_BWT_SUFFIXES);
         if (rc) return rc;
@@ -331,6 +341,10 @@ static int run_batch(rcx_ctx* c, int codec, const rcx_batch* b, const uint32_t* 
         if (in_span && pieces <= 1) HIPCHK(c, hipMemcpyAsync(c->d_in.p, b->in_base, in_span, hipMemcpyHostToDevice, s));
         d_in = (const uint8_t*)c->d_in.p;
         d_out = (uint8_t*)c->d_out.p + out_shift;
+        // the DEFLATE encoders promise that no byte of the caller's buffer outside the streams they write changes: the copy back below
+        // takes the whole span, so the span starts as the caller's bytes
+        if ((codec == RCX_DEFLATE_ENCODE || codec == RCX_ZLIB_ENCODE || codec == RCX_GZIP_ENCODE) && out_span)
+            HIPCHK(c, hipMemcpyAsync(d_out, b->out_base, out_span, hipMemcpyHostToDevice, s));
     } else if (b->mem != RCX_MEM_DEVICE) { c->err = "bad mem kind"; return RCX_RC_BAD_ARG; }
 
     const size_t N = n;
@@ -366,6 +380,11 @@ static int run_batch(rcx_ctx* c, int codec, const rcx_batch* b, const uint32_t* 
     k.status = (int32_t*)(d64 + 7 * N); k.aux = (uint32_t*)(k.status + N);
     k.nblocks = n;
     uint64_t sb = rcx_scratch_bytes(codec, n, codec == RCX_BWT_SUFFIXES ? max_in : max_block);
+    if (codec == RCX_DEFLATE_ENCODE || codec == RCX_ZLIB_ENCODE || codec == RCX_GZIP_ENCODE) {      // the staging of the real segments
+        uint64_t segs = 0;
+        for (uint32_t i = 0; i < n; i++) segs += rcx_tu_deflate_encode_segments(b->in_len[i]);
+        sb = rcx_tu_deflate_encode_scratch(n, segs);
+    }
     if (codec == RCX_DC_ENCODE && param_over > 0) sb = 0;          // withctx: the wave-per-block kernel encodes, no chunk states
     if (codec == RCX_DC_ENCODE && sb && c->d_scratch.reserve(sb + 64) != hipSuccess) {
         // the chunk states are optional (37 KiB a block): a batch too large for them falls back to the wave-per-block kernel
@@ -550,6 +569,9 @@ extern "C" int rcx_zlib_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* f
 extern "C" int rcx_adler32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* adler) { return run_batch(c, RCX_ADLER32, b, nullptr, adler, nullptr, false); }
 extern "C" int rcx_crc32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* crc) { return run_batch(c, RCX_CRC32, b, nullptr, crc, nullptr, false); }
 extern "C" int rcx_gzip_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, RCX_GZIP_DECODE, b, nullptr, flags, nullptr, true); }
+extern "C" int rcx_deflate_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_DEFLATE_ENCODE, b, nullptr, nullptr, nullptr, true); }
+extern "C" int rcx_zlib_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_ZLIB_ENCODE, b, nullptr, nullptr, nullptr, true); }
+extern "C" int rcx_gzip_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_GZIP_ENCODE, b, nullptr, nullptr, nullptr, true); }
 extern "C" int rcx_bwt_forward_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, RCX_BWT_FORWARD, b, nullptr, origin, nullptr, true); }
 extern "C" int rcx_bwt_suffixes_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, RCX_BWT_SUFFIXES, b, nullptr, origin, nullptr, true); }
 extern "C" int rcx_bwt_inversion_table_batch(rcx_ctx* c, const rcx_batch* b, const uint32_t* origin) { return run_batch(c, RCX_BWT_INVERSION_TABLE, b, origin, nullptr, nullptr, true); }

@@ -32,3 +32,7 @@ uint64_t rcx_tu_bwt_inverse_scratch(uint32_t nblocks, uint64_t max_block);
 // tu_serial.hip
 void rcx_tu_serial(hipStream_t s, int codec, rcx_kargs& k, int variant, uint32_t param);
 uint64_t rcx_tu_dc_encode_scratch(uint32_t nblocks, uint64_t max_block);
+// tu_deflate_encode.hip (fmt: 0 raw DEFLATE, 1 zlib, 2 gzip)
+int rcx_tu_deflate_encode(hipStream_t s, rcx_kargs& k, int fmt, std::string& err);
+uint64_t rcx_tu_deflate_encode_scratch(uint32_t nblocks, uint64_t nsegs);
+uint64_t rcx_tu_deflate_encode_segments(uint64_t len);

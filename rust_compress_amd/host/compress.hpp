@@ -10,6 +10,7 @@
 //
 //   compress::lz4::{Decoder,Encoder,decode_block,encode_block,compression_bound}   src/lz4.rs
 //   compress::flate::Decoder, compress::zlib::Decoder, compress::Adler32           src/flate.rs, zlib.rs, adler.rs
+//   compress::flate::Encoder, compress::zlib::Encoder (extension: the reference has no DEFLATE encoder)
 //   compress::bwt::{Encoder,Decoder,encode_simple,decode_simple}, bwt::mtf, bwt::dc src/bwt/*.rs
 //   compress::entropy::ari::{ByteEncoder,ByteDecoder}                              src/entropy/ari/table.rs
 //   compress::entropy::ari::{RangeEncoder,Model,Encoder,Decoder,table,bin,apm}     src/entropy/ari/*.rs (ari_symbol.hpp)
@@ -408,8 +409,27 @@ template <class Fn> ManyResult decode_many(const std::vector<std::vector<uint8_t
     for (int st : status) raise_status(st);                                       // the first stream that failed, as its own Decoder would
     return m;
 }
+// the DEFLATE encoders (extension: the reference has none): the whole input as ONE stream at finish(); write() only buffers
+template <class W, int (*Call)(rcx_ctx*, const rcx_batch*), uint64_t Framing>
+class OneShotEncoder {
+public:
+    explicit OneShotEncoder(W w) : w_(std::move(w)) {}
+    size_t write(const uint8_t* p, size_t n) { buf_.insert(buf_.end(), p, p + n); return n; }
+    void write_all(const uint8_t* p, size_t n) { write(p, n); }
+    W finish()
+    {
+        auto r = run_batch({buf_}, {rcx_deflate_compression_bound(buf_.size()) + Framing}, [](rcx_ctx* c, rcx_batch* b, uint32_t*) { return Call(c, b); });
+        check(r);
+        w_.write(r.out[0].data(), r.out[0].size());
+        buf_.clear();
+        return std::move(w_);
+    }
+private:
+    W w_; std::vector<uint8_t> buf_;
+};
 }  // namespace detail
 namespace flate {
+template <class W> using Encoder = detail::OneShotEncoder<W, rcx_deflate_encode_batch, 0>;   // one raw DEFLATE stream (RFC 1951)
 // many raw DEFLATE streams, ONE batch call (the reference decodes one deflate block per read(), flate.rs:468-488: a stream is one wave's work
 // on the GPU -- a caller with many streams hands them over together)
 inline detail::ManyResult decode_many(const std::vector<std::vector<uint8_t>>& streams)
@@ -424,6 +444,7 @@ public:
 };
 }  // namespace flate
 namespace zlib {
+template <class W> using Encoder = detail::OneShotEncoder<W, rcx_zlib_encode_batch, 6>;      // one zlib stream (RFC 1950)
 inline detail::ManyResult decode_many(const std::vector<std::vector<uint8_t>>& members)      // every member's Adler-32 checked on the device
 { return detail::decode_many(members, [](rcx_ctx* c, rcx_batch* b, uint32_t* f) { return rcx_zlib_decode_batch(c, b, f); }); }
 template <class R>
