@@ -8,13 +8,20 @@ blocks are independent -- SURVEY.md 8e).  One JSON line is printed by rank 0.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment re-launches itself under
 `torch.distributed.run` with one rank per GPU; launched by the driver under torch.distributed.run it reads
-RANK / LOCAL_RANK / WORLD_SIZE as given.  Besides the kernel-only headline value the line carries
+RANK / LOCAL_RANK / WORLD_SIZE as given.
+
+A plain run measures the headline alone: it builds the workload, checks the decoder's output against the source (untimed),
+runs the W warm-up and K timed steps, writes --dump-outputs if asked and prints the line.  With `--full` (the --no-*
+options leave legs out of it) the line also carries
+  * `per_distribution` (G-runs, G-rand) and `sustained`: the other distributions of config 2, two seconds back to back;
   * `end_to_end`: the same job when the compressed blocks live on rank 0 -- root scatter of the compressed ranges,
     decode, root gather of the decoded ranges (RCCL grouped send/recv, rust_compress_amd/dist.py), timed per phase;
   * `other_configs` (N=1): BASELINE configs 3, 4, 5 from the same process (benchmarks/bench_configs.py);
+  * `host_path` (N=1): the same blocks through the host-memory entry point;
   * `hbm_ceiling_measured`: a device-to-device copy (the library's own 16-bytes-a-lane kernel), next to the 8 TB/s spec peak the roofline uses;
   * `single_stream` (N=1): one LZ4 block / one 1 MiB DEFLATE stream / one BWT block alone on the GPU, batches of 1..4096, break-even sizes;
-  * `cpu_baseline` (N=1): the oracle on the host cores.
+  * `cpu_baseline` (N=1): the oracle on the host cores;
+  * `extras` (with --extras): every distribution under every kernel variant.
 Inputs are synthetic (rust_compress_amd.synth) and are compressed on the GPU by the product's own bit-exact LZ4 encoder;
 the oracle is used only for the cpu_baseline leg (and its parity check).
 
@@ -682,15 +689,18 @@ def main():
     ap.add_argument("--kind", default="text", help="synthetic distribution: text|runs|rand|mix")
     ap.add_argument("--variant", type=int, default=0, help="kernel variant (A/B)")
     ap.add_argument("--nblocks", type=int, default=NBLOCKS)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the scatter / decode / gather leg")
-    ap.add_argument("--no-others", action="store_true", help="skip BASELINE configs 3-5 and the HBM ceiling")
-    ap.add_argument("--no-dists", action="store_true", help="skip config 2's other distributions (G-runs, G-rand)")
-    ap.add_argument("--others-scale", type=float, default=1.0, help="fraction of the full size of configs 3-5")
-    ap.add_argument("--extras", action="store_true", help="also time the other distributions / variants")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run every side leg (see the module docstring)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the scatter / decode / gather leg")
+    ap.add_argument("--no-others", action="store_true", help="with --full: skip BASELINE configs 3-5 and the HBM ceiling")
+    ap.add_argument("--no-dists", action="store_true", help="with --full: skip config 2's other distributions (G-runs, G-rand)")
+    ap.add_argument("--others-scale", type=float, default=1.0, help="with --full: fraction of the full size of configs 3-5")
+    ap.add_argument("--extras", action="store_true", help="with --full: also time the other distributions / variants")
     ap.add_argument("--dry-gloo", action="store_true", help="CPU test of the multi-rank plumbing (see the module docstring)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.extras and not args.full:
+        ap.error("--extras is a side leg: it needs --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_spawn(args))
@@ -701,7 +711,7 @@ def main():
     eng = (DryEngine if args.dry_gloo else GpuEngine)(args, local_rank)
     torch = eng.torch
     dist = None
-    want_dist = world > 1 or not args.no_e2e or os.environ.get("RCX_BENCH_FORCE_DIST")
+    want_dist = world > 1 or (args.full and not args.no_e2e) or os.environ.get("RCX_BENCH_FORCE_DIST")
     if want_dist:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -743,10 +753,10 @@ def main():
     if args.dump_outputs and rank == 0:                         # (untimed, and before any side leg launches the decoder again)
         dump_outputs(eng, wl, args.dump_outputs)
 
-    # ---- the headline is complete here.  Rank 0 stashes the line now; everything below is a SIDE LEG that runs under
-    # SideLegs.run (every rank catches, one all_reduce(MAX) of an error flag decides together whether the ranks can go on
-    # using the process group) and under a watchdog that prints the stashed line if the legs do not come back in time:
-    # no failure or hang after this point can cost the headline value.
+    # ---- the headline is complete here: a plain run prints its line and ends.  With --full, rank 0 stashes the line now;
+    # everything below is a SIDE LEG that runs under SideLegs.run (every rank catches, one all_reduce(MAX) of an error flag
+    # decides together whether the ranks can go on using the process group) and under a watchdog that prints the stashed
+    # line if the legs do not come back in time: no failure or hang after this point can cost the headline value.
     comp_total = float(tot[1].item())
     res = None
     if rank == 0:
@@ -790,6 +800,10 @@ def main():
             "end_to_end": None,
         }
     legs = SideLegs(eng, dist, rank, world, res)
+    if not args.full:                                           # a plain run: the headline line and nothing more
+        legs.finish()
+        eng.close()
+        return
     legs.start_watchdog(float(os.environ.get("RCX_BENCH_SIDE_TIMEOUT", "900")))
 
     # ---- config 2's other distributions (reported separately), same timing discipline, every rank

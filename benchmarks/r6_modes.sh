@@ -3,7 +3,7 @@
 for f in "$@"; do
   RCX_EXTRA_FLAGS="$f" python -c "from rust_compress_amd.csrc import build; build.build()" 2>&1 | grep -i " error" | head -3
   for i in 1 2; do
-  RCX_EXTRA_FLAGS="$f" timeout 300 python bench.py --no-cpu --no-e2e --no-others --steps 40 --warmup 20 2>/dev/null | python -c "
+  RCX_EXTRA_FLAGS="$f" timeout 300 python bench.py --full --no-cpu --no-e2e --no-others --steps 40 --warmup 20 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,5 +1,6 @@
-"""CPU suite: `bench.py --gpus N` really starts N ranks and its end-to-end leg (root scatter -> decode -> root gather)
-moves the right bytes.  Runs the benchmark's own code on gloo with the oracle as the block codec (--dry-gloo)."""
+"""CPU suite: `bench.py --gpus N` really starts N ranks, its end-to-end leg (root scatter -> decode -> root gather, with
+--full) moves the right bytes, and a plain run is the headline alone.  Runs the benchmark's own code on gloo with the
+oracle as the block codec (--dry-gloo)."""
 import importlib
 import json
 import os
@@ -18,7 +19,7 @@ def test_bench_gpus_n_spawns_n_ranks(gpus, oracle):
     env = dict(os.environ, RCX_BENCH_DRY_CODEC="_dry_codec", PYTHONPATH=os.path.join(ROOT, "tests") + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dry-gloo", "--nblocks", "5", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dry-gloo", "--full", "--nblocks", "5", "--steps", "2", "--warmup", "1"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -44,7 +45,7 @@ def test_bench_line_survives_a_rank_failing_inside_the_scatter(gpus, oracle):
                PYTHONPATH=os.path.join(ROOT, "tests") + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dry-gloo", "--nblocks", "5", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dry-gloo", "--full", "--nblocks", "5", "--steps", "2", "--warmup", "1"],
                        env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]
@@ -62,7 +63,7 @@ def test_bench_watchdog_prints_the_line_when_a_leg_hangs(oracle):
                PYTHONPATH=os.path.join(ROOT, "tests") + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-gloo", "--nblocks", "5", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-gloo", "--full", "--nblocks", "5", "--steps", "2", "--warmup", "1"],
                        env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]
@@ -74,12 +75,36 @@ def test_bench_single_rank_dry(oracle):
     env = dict(os.environ, RCX_BENCH_DRY_CODEC="_dry_codec", PYTHONPATH=os.path.join(ROOT, "tests") + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-gloo", "--nblocks", "4", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-gloo", "--full", "--nblocks", "4", "--steps", "2", "--warmup", "1"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     res = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["end_to_end"]["verified"] is True and res["end_to_end"]["bytes_gathered"] == 0
     assert res["other_configs"][0]["sharded_container_verified"] is True
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_is_the_headline_alone(gpus, oracle):
+    """Without --full the line is the headline and nothing more: no side leg runs, on one rank or several.  The faulty codec
+    would make rank 1's end-to-end leg raise, so a plain run at world 2 that reached it would report a failed leg."""
+    env = dict(os.environ, RCX_BENCH_DRY_CODEC="_dry_codec_faulty", RCX_DRY_FAULT_RANK="1",
+               PYTHONPATH=os.path.join(ROOT, "tests") + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dry-gloo", "--nblocks", "4", "--steps", "3", "--warmup", "1"],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["metric"] == "GiB/s decoded output (batched blocks)" and res["unit"] == "GiB/s" and res["higher_is_better"] is True
+    assert res["dtype"] == "u8" and res["value"] > 0 and res["ms_per_step"] > 0 and res["steps"] == 3 and res["warmup"] == 1
+    assert res["n_gpus"] == gpus and res["end_to_end"] is None and list(res["per_distribution"]) == ["G-text"]
+    side = ("other_configs", "sustained", "host_path", "cpu_baseline", "single_stream", "hbm_ceiling_measured", "extras",
+            "rccl_self_sendrecv", "side_legs_failed", "side_legs_note")
+    assert not [k for k in side if k in res]
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-gloo", "--extras"], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 2 and "--full" in p.stderr
 
 
 def test_container_split_join(oracle):
