@@ -191,6 +191,24 @@ int rcx_zlib_encode_batch(rcx_ctx*, const rcx_batch*);
 int rcx_gzip_encode_batch(rcx_ctx*, const rcx_batch*);
 /* largest raw DEFLATE stream of n input bytes; a zlib stream needs 6 bytes more, a gzip member 18 */
 uint64_t rcx_deflate_compression_bound(uint64_t n);
+/* The same encoders at a compression level of 1..9.  Level 1 is rcx_*_encode_batch, byte for byte.  Levels 2..9 search hash chains
+ * of 4-byte prefixes for every position's longest match (at most 258 bytes, 32 KiB back, also across the internal segments) up to a
+ * depth that grows with the level, then choose the tokens by a min-cost parse priced in bits by Huffman code lengths of a first
+ * parse (the greedy one); from level 7 on the parse runs a second time, priced by the first one's own code lengths:
+ *     level   1       2  3   4   5   6   7   8    9
+ *     depth   greedy  4  8  16  32  64  96  160  256
+ *     parses  -       1  1   1   1   1   2   2    2
+ * Each block is still the cheapest of stored, fixed, dynamic Huffman and dynamic all-literals, so rcx_deflate_compression_bound
+ * holds at every level.  Header fields by level, as zlib sets them: zlib FLEVEL 78 01 (level 1), 78 5E (2-5), 78 9C (6), 78 DA
+ * (7-9); gzip XFL 2 at level 9, else 0.  Statuses, slots, determinism and the 2^32 - 1 byte limit as above.  A level outside 1..9
+ * returns RCX_RC_BAD_ARG.  rcx_launch_dev(ctx, RCX_{DEFLATE,ZLIB,GZIP}_ENCODE, ...) runs level rcx_ctx_set_param(ctx, codec, level):
+ * 0 (the default) and 1 the level-1 encoder, 2..9 these, anything else RCX_RC_BAD_ARG; levels 2..9 need
+ * rcx_deflate_level_scratch_bytes(nblocks, max_block) of scratch (enough for any level and framing): too little and the streams it
+ * does not cover get RCX_E_MALFORMED. */
+int rcx_deflate_encode_level_batch(rcx_ctx*, const rcx_batch*, int level);
+int rcx_zlib_encode_level_batch(rcx_ctx*, const rcx_batch*, int level);
+int rcx_gzip_encode_level_batch(rcx_ctx*, const rcx_batch*, int level);
+uint64_t rcx_deflate_level_scratch_bytes(uint32_t nblocks, uint64_t max_block);
 
 /* ---- BWT / MTF / DC --------------------------------------------------------- */
 /* reference: src/bwt/mod.rs:136-219 compute_suffixes + TransformIterator.
@@ -312,7 +330,9 @@ int rcx_hbm_copy_probe(rcx_ctx*, uint64_t bytes, int reps, double* gb_per_s);
 int rcx_ctx_set_variant(rcx_ctx*, int codec, int variant);
 /* codec parameter for rcx_launch_dev (the *_batch entry points take it as an argument): the rate of RCX_ARI_BINARY_*;
  * RCX_LZ4_DECODE: bit 0 = host-memory batches by plain copies (see rcx_lz4_decode_batch), bits 8-15 / 16-23 tuning of the ranges;
- * RCX_LZ4_ENCODE: 0 = the reference's encoder, 1..12 = the HC level (see rcx_lz4_encode_hc_batch); the batch calls ignore it */
+ * RCX_LZ4_ENCODE: 0 = the reference's encoder, 1..12 = the HC level (see rcx_lz4_encode_hc_batch); the batch calls ignore it;
+ * RCX_DEFLATE_ENCODE / RCX_ZLIB_ENCODE / RCX_GZIP_ENCODE: 0 or 1..9 = the level (see rcx_deflate_encode_level_batch); the batch calls
+ * ignore it */
 int rcx_ctx_set_param(rcx_ctx*, int codec, uint32_t value);
 
 /* ---- more than one device ---------------------------------

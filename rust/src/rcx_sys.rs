@@ -143,6 +143,10 @@ extern "C" {
     pub fn rcx_zlib_encode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch) -> c_int;
     pub fn rcx_gzip_encode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch) -> c_int;
     pub fn rcx_deflate_compression_bound(n: u64) -> u64;
+    pub fn rcx_deflate_encode_level_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int) -> c_int;
+    pub fn rcx_zlib_encode_level_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int) -> c_int;
+    pub fn rcx_gzip_encode_level_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int) -> c_int;
+    pub fn rcx_deflate_level_scratch_bytes(nblocks: u32, max_block: u64) -> u64;
     // ---- BWT / MTF / DC (src/bwt/mod.rs, mtf.rs, dc.rs)
     pub fn rcx_bwt_forward_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;
     pub fn rcx_bwt_suffixes_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;

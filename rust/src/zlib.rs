@@ -2,6 +2,7 @@
 use crate::rcx_sys::*;
 use crate::{decode_many_with, grow_decode, run_batch, Buffered, TailReader};
 use std::io::{self, Read, Write};
+use std::os::raw::c_int;
 
 pub struct Decoder<R: Read> {
     r: TailReader<R>,
@@ -40,15 +41,25 @@ pub fn decode_many(members: &[&[u8]]) -> io::Result<Vec<(Vec<u8>, usize)>> {
 pub struct Encoder<W: Write> {
     w: W,
     buf: Vec<u8>,
+    level: u32,
 }
 
 impl<W: Write> Encoder<W> {
     pub fn new(w: W) -> Encoder<W> {
-        Encoder { w, buf: Vec::new() }
+        Encoder { w, buf: Vec::new(), level: 0 }
+    }
+    /// Extension: compression level 1..9 (`rcx_zlib_encode_level_batch`; 1 makes the bytes of `new`).  Panics on a level outside 1..9.
+    pub fn with_level(w: W, level: u32) -> Encoder<W> {
+        assert!((1..=9).contains(&level), "deflate level must be 1..9");
+        Encoder { level, ..Encoder::new(w) }
     }
     pub fn finish(mut self) -> (W, io::Result<()>) {
         let cap = unsafe { rcx_deflate_compression_bound(self.buf.len() as u64) } + 6;
-        let r = run_batch(&[&self.buf[..]], &[cap], |c, b, _| unsafe { rcx_zlib_encode_batch(c, b) }).check();
+        let level = self.level as c_int;
+        let r = run_batch(&[&self.buf[..]], &[cap], |c, b, _| unsafe {
+            if level == 0 { rcx_zlib_encode_batch(c, b) } else { rcx_zlib_encode_level_batch(c, b, level) }
+        })
+        .check();
         let res = match r {
             Ok(r) => self.w.write_all(&r.out[0]),
             Err(e) => Err(e),

@@ -43,6 +43,7 @@ EXPORTS = [
     "rcx_hbm_copy_probe", "rcx_multi_scatter_dev", "rcx_multi_gather_dev", "rcx_multi_transport",
     "rcx_deflate_encode_batch", "rcx_zlib_encode_batch", "rcx_gzip_encode_batch", "rcx_deflate_compression_bound",
     "rcx_lz4_encode_hc_batch", "rcx_lz4_hc_scratch_bytes",
+    "rcx_deflate_encode_level_batch", "rcx_zlib_encode_level_batch", "rcx_gzip_encode_level_batch", "rcx_deflate_level_scratch_bytes",
 ]
 
 
@@ -107,6 +108,10 @@ def lib():
         L.rcx_lz4_encode_hc_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int]
         L.rcx_lz4_hc_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64]
         L.rcx_lz4_hc_scratch_bytes.restype = C.c_uint64
+        for name in ("rcx_deflate_encode_level_batch", "rcx_zlib_encode_level_batch", "rcx_gzip_encode_level_batch"):
+            getattr(L, name).argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int]
+        L.rcx_deflate_level_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64]
+        L.rcx_deflate_level_scratch_bytes.restype = C.c_uint64
         for name in ("rcx_inflate_batch", "rcx_zlib_decode_batch", "rcx_adler32_batch", "rcx_crc32_batch",
                      "rcx_gzip_decode_batch", "rcx_bwt_forward_batch",
                      "rcx_bwt_inverse_batch", "rcx_bwt_inverse_minimal_batch", "rcx_dc_decode_batch", "rcx_dc_decode_ctx_batch",

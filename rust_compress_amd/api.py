@@ -131,18 +131,24 @@ class Context:
         """One gzip member (RFC 1952) per blob: header, DEFLATE, CRC32 + ISIZE (extension)."""
         return self._run_host("rcx_gzip_decode_batch", blobs, caps, extra_out=True)
 
-    def deflate_encode(self, blobs, caps=None):
+    def _deflate_encode(self, fn, blobs, caps, framing, level):
+        caps = caps if caps is not None else [deflate_bound(len(b)) + framing for b in blobs]
+        if level == 1:
+            return self._run_host(fn + "_batch", blobs, caps)
+        return self._run_host(fn + "_level_batch", blobs, caps, scalar=int(level))
+
+    def deflate_encode(self, blobs, caps=None, level=1):
         """One raw DEFLATE stream (RFC 1951) per blob (extension: the reference has no DEFLATE encoder).  caps default to
-        rcx_deflate_compression_bound."""
-        return self._run_host("rcx_deflate_encode_batch", blobs, caps if caps is not None else [deflate_bound(len(b)) for b in blobs])
+        rcx_deflate_compression_bound.  level 1..9 (rcx_deflate_encode_level_batch; 1 is the default encoder's bytes)."""
+        return self._deflate_encode("rcx_deflate_encode", blobs, caps, 0, level)
 
-    def zlib_encode(self, blobs, caps=None):
-        """One zlib stream (RFC 1950: 78 01, DEFLATE, Adler-32) per blob; caps default to the DEFLATE bound + 6."""
-        return self._run_host("rcx_zlib_encode_batch", blobs, caps if caps is not None else [deflate_bound(len(b)) + 6 for b in blobs])
+    def zlib_encode(self, blobs, caps=None, level=1):
+        """One zlib stream (RFC 1950: 78 01 at level 1, DEFLATE, Adler-32) per blob; caps default to the DEFLATE bound + 6."""
+        return self._deflate_encode("rcx_zlib_encode", blobs, caps, 6, level)
 
-    def gzip_encode(self, blobs, caps=None):
+    def gzip_encode(self, blobs, caps=None, level=1):
         """One gzip member (RFC 1952, no optional header fields, MTIME 0, OS 255) per blob; caps default to the DEFLATE bound + 18."""
-        return self._run_host("rcx_gzip_encode_batch", blobs, caps if caps is not None else [deflate_bound(len(b)) + 18 for b in blobs])
+        return self._deflate_encode("rcx_gzip_encode", blobs, caps, 18, level)
 
     def bwt_forward(self, blobs):
         return self._run_host("rcx_bwt_forward_batch", blobs, [len(b) for b in blobs], extra_out=True)

@@ -401,12 +401,14 @@ class lz4:
 class _OneShotEncoder:
     """DEFLATE / zlib / gzip Encoder (extension: the reference has no DEFLATE encoder).  Shaped like lz4.Encoder, but it HOLDS its input:
     write() only buffers, there is no incremental state across write() calls, and finish() encodes everything as ONE stream in one
-    batch call, writes it to the writer and returns the writer."""
+    batch call, writes it to the writer and returns the writer.  level: None (today's bytes, level 1) or 1..9; anything else raises
+    ValueError."""
     _call = None
 
-    def __init__(self, w):
+    def __init__(self, w, level=None):
         self.w = w
         self.buf = bytearray()
+        self.level = _deflate_level(level)
 
     def write(self, buf):
         self.buf += bytes(buf)
@@ -416,14 +418,24 @@ class _OneShotEncoder:
         pass
 
     def finish(self):
-        res = _check(getattr(context(), self._call)([bytes(self.buf)]))
+        res = _check(getattr(context(), self._call)([bytes(self.buf)], level=self.level))
         self.buf = bytearray()
         self.w.write(res.outputs[0])
         return self.w
 
     @classmethod
-    def _encode_many(cls, blobs):
-        return _check(getattr(context(), cls._call)([bytes(b) for b in blobs])).outputs
+    def _encode_many(cls, blobs, level=None):
+        level = _deflate_level(level)
+        return _check(getattr(context(), cls._call)([bytes(b) for b in blobs], level=level)).outputs
+
+
+def _deflate_level(level):
+    """None: level 1, the default encoder's bytes; else 1..9 (extension: rcx_deflate_encode_level_batch and its framings)"""
+    if level is None:
+        return 1
+    if not 1 <= int(level) <= 9:
+        raise ValueError("deflate level must be 1..9 (or None: level 1)")
+    return int(level)
 
 
 class flate:
@@ -444,9 +456,9 @@ class flate:
         _call = "deflate_encode"
 
     @staticmethod
-    def encode_many(blobs):
-        """-> [bytes], one raw DEFLATE stream per input, all encoded by ONE batch call"""
-        return flate.Encoder._encode_many(blobs)
+    def encode_many(blobs, level=None):
+        """-> [bytes], one raw DEFLATE stream per input, all encoded by ONE batch call (level: as the Encoder's)"""
+        return flate.Encoder._encode_many(blobs, level)
 
 
 class zlib:
@@ -465,9 +477,9 @@ class zlib:
         _call = "zlib_encode"
 
     @staticmethod
-    def encode_many(blobs):
-        """-> [bytes], one zlib stream per input, all encoded by ONE batch call"""
-        return zlib.Encoder._encode_many(blobs)
+    def encode_many(blobs, level=None):
+        """-> [bytes], one zlib stream per input, all encoded by ONE batch call (level: as the Encoder's)"""
+        return zlib.Encoder._encode_many(blobs, level)
 
 
 class gzip:
@@ -504,9 +516,9 @@ class gzip:
         _call = "gzip_encode"
 
     @staticmethod
-    def encode_many(blobs):
-        """-> [bytes], one gzip member per input, all encoded by ONE batch call"""
-        return gzip.Encoder._encode_many(blobs)
+    def encode_many(blobs, level=None):
+        """-> [bytes], one gzip member per input, all encoded by ONE batch call (level: as the Encoder's)"""
+        return gzip.Encoder._encode_many(blobs, level)
 
 
 class Crc32:                                           # extension, mirrors Adler32 below

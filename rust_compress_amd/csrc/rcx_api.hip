@@ -146,6 +146,10 @@ extern "C" uint64_t rcx_ari_byte_encode_bound(uint64_t n) { return 2 * n + 16; }
 extern "C" uint64_t rcx_rle_encode_bound(uint64_t n) { return n + n / 2 + 16; }
 // a 64 KiB segment is at worst two stored blocks: 2 x (3 header bits + 7 padding + 32 LEN/NLEN) = 84 bits <= 11 bytes; empty input: 2 bytes
 extern "C" uint64_t rcx_deflate_compression_bound(uint64_t n) { return n + 11 * rcx_tu_deflate_encode_segments(n) + 2; }
+extern "C" uint64_t rcx_deflate_level_scratch_bytes(uint32_t nblocks, uint64_t max_block)
+{
+    return rcx_tu_deflate_level_scratch(nblocks, (uint64_t)nblocks * rcx_tu_deflate_encode_segments(max_block));
+}
 extern "C" uint64_t rcx_lz4_hc_scratch_bytes(uint32_t nblocks, uint64_t max_block)
 {
     return rcx_tu_lz4_hc_scratch(nblocks, (uint64_t)nblocks * rcx_tu_lz4_hc_segments(max_block));
@@ -203,8 +207,11 @@ static int launch_codec(rcx_ctx* c, int codec, rcx_kargs& k, int param_over = -1
         if (k.scratch_bytes < rcx_tu_gzip_scratch(n)) { c->err = "gzip decode: scratch too small"; return RCX_RC_BAD_ARG; }
         rcx_tu_gzip_decode(s, k, v);
         break;
-    case RCX_DEFLATE_ENCODE: case RCX_ZLIB_ENCODE: case RCX_GZIP_ENCODE: {
-        int rc = rcx_tu_deflate_encode(s, k, codec == RCX_DEFLATE_ENCODE ? 0 : codec == RCX_ZLIB_ENCODE ? 1 : 2, c->err);
+    case RCX_DEFLATE_ENCODE: case RCX_ZLIB_ENCODE: case RCX_GZIP_ENCODE: {   // the codec parameter: the level, 0 (as 1) or 1..9
+        const uint32_t level = param_over >= 0 ? (uint32_t)param_over : c->param[codec];
+        if (level > 9) { c->err = "deflate encode: level must be 0 or 1..9"; return RCX_RC_BAD_ARG; }
+        const int fmt = codec == RCX_DEFLATE_ENCODE ? 0 : codec == RCX_ZLIB_ENCODE ? 1 : 2;
+        int rc = level > 1 ? rcx_tu_deflate_encode_level(s, k, fmt, (int)level, c->err) : rcx_tu_deflate_encode(s, k, fmt, c->err);
         if (rc) return rc;
         break; }
     case RCX_BWT_FORWARD: case RCX_BWT_SUFFIXES: {
@@ -390,7 +397,7 @@ static int run_batch(rcx_ctx* c, int codec, const rcx_batch* b, const uint32_t* 
     if (codec == RCX_DEFLATE_ENCODE || codec == RCX_ZLIB_ENCODE || codec == RCX_GZIP_ENCODE) {      // the staging of the real segments
         uint64_t segs = 0;
         for (uint32_t i = 0; i < n; i++) segs += rcx_tu_deflate_encode_segments(b->in_len[i]);
-        sb = rcx_tu_deflate_encode_scratch(n, segs);
+        sb = param_over > 1 ? rcx_tu_deflate_level_scratch(n, segs) : rcx_tu_deflate_encode_scratch(n, segs);   // (+ chains, parse: levels 2..9)
     }
     if (codec == RCX_LZ4_ENCODE && param_over > 0) {                // HC: the chains and parse of the real segments
         uint64_t segs = 0;
@@ -587,9 +594,18 @@ extern "C" int rcx_zlib_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* f
 extern "C" int rcx_adler32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* adler) { return run_batch(c, RCX_ADLER32, b, nullptr, adler, nullptr, false); }
 extern "C" int rcx_crc32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* crc) { return run_batch(c, RCX_CRC32, b, nullptr, crc, nullptr, false); }
 extern "C" int rcx_gzip_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, RCX_GZIP_DECODE, b, nullptr, flags, nullptr, true); }
-extern "C" int rcx_deflate_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_DEFLATE_ENCODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_zlib_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_ZLIB_ENCODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_gzip_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_GZIP_ENCODE, b, nullptr, nullptr, nullptr, true); }
+extern "C" int rcx_deflate_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_DEFLATE_ENCODE, b, nullptr, nullptr, nullptr, true, 1); }
+extern "C" int rcx_zlib_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_ZLIB_ENCODE, b, nullptr, nullptr, nullptr, true, 1); }
+extern "C" int rcx_gzip_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_GZIP_ENCODE, b, nullptr, nullptr, nullptr, true, 1); }
+static int deflate_level_batch(rcx_ctx* c, int codec, const rcx_batch* b, int level)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    if (level < 1 || level > 9) { c->err = "deflate encode: level must be 1..9"; return RCX_RC_BAD_ARG; }
+    return run_batch(c, codec, b, nullptr, nullptr, nullptr, true, level);
+}
+extern "C" int rcx_deflate_encode_level_batch(rcx_ctx* c, const rcx_batch* b, int level) { return deflate_level_batch(c, RCX_DEFLATE_ENCODE, b, level); }
+extern "C" int rcx_zlib_encode_level_batch(rcx_ctx* c, const rcx_batch* b, int level) { return deflate_level_batch(c, RCX_ZLIB_ENCODE, b, level); }
+extern "C" int rcx_gzip_encode_level_batch(rcx_ctx* c, const rcx_batch* b, int level) { return deflate_level_batch(c, RCX_GZIP_ENCODE, b, level); }
 extern "C" int rcx_bwt_forward_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, RCX_BWT_FORWARD, b, nullptr, origin, nullptr, true); }
 extern "C" int rcx_bwt_suffixes_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, RCX_BWT_SUFFIXES, b, nullptr, origin, nullptr, true); }
 extern "C" int rcx_bwt_inversion_table_batch(rcx_ctx* c, const rcx_batch* b, const uint32_t* origin) { return run_batch(c, RCX_BWT_INVERSION_TABLE, b, origin, nullptr, nullptr, true); }

@@ -36,6 +36,8 @@ uint64_t rcx_tu_dc_encode_scratch(uint32_t nblocks, uint64_t max_block);
 int rcx_tu_deflate_encode(hipStream_t s, rcx_kargs& k, int fmt, std::string& err);
 uint64_t rcx_tu_deflate_encode_scratch(uint32_t nblocks, uint64_t nsegs);
 uint64_t rcx_tu_deflate_encode_segments(uint64_t len);
+int rcx_tu_deflate_encode_level(hipStream_t s, rcx_kargs& k, int fmt, int level, std::string& err);    // level 1..9 (1: as above)
+uint64_t rcx_tu_deflate_level_scratch(uint32_t nblocks, uint64_t nsegs);
 // tu_lz4_hc.hip (level 1..12)
 int rcx_tu_lz4_hc(hipStream_t s, rcx_kargs& k, int level, std::string& err);
 uint64_t rcx_tu_lz4_hc_scratch(uint32_t nblocks, uint64_t nsegs);

@@ -443,27 +443,31 @@ template <class Fn> ManyResult decode_many(const std::vector<std::vector<uint8_t
     for (int st : status) raise_status(st);                                       // the first stream that failed, as its own Decoder would
     return m;
 }
-// the DEFLATE encoders (extension: the reference has none): the whole input as ONE stream at finish(); write() only buffers
-template <class W, int (*Call)(rcx_ctx*, const rcx_batch*), uint64_t Framing>
+// the DEFLATE encoders (extension: the reference has none): the whole input as ONE stream at finish(); write() only buffers.
+// level 0 (the default): the level-1 encoder's bytes; 1..9: rcx_*_encode_level_batch; anything else throws (RCX_RC_BAD_ARG) at finish()
+template <class W, int (*Call)(rcx_ctx*, const rcx_batch*), int (*CallLevel)(rcx_ctx*, const rcx_batch*, int), uint64_t Framing>
 class OneShotEncoder {
 public:
-    explicit OneShotEncoder(W w) : w_(std::move(w)) {}
+    explicit OneShotEncoder(W w, int level = 0) : w_(std::move(w)), level_(level) {}
     size_t write(const uint8_t* p, size_t n) { buf_.insert(buf_.end(), p, p + n); return n; }
     void write_all(const uint8_t* p, size_t n) { write(p, n); }
     W finish()
     {
-        auto r = run_batch({buf_}, {rcx_deflate_compression_bound(buf_.size()) + Framing}, [](rcx_ctx* c, rcx_batch* b, uint32_t*) { return Call(c, b); });
+        const int level = level_;
+        auto r = run_batch({buf_}, {rcx_deflate_compression_bound(buf_.size()) + Framing}, [level](rcx_ctx* c, rcx_batch* b, uint32_t*) {
+            return level ? CallLevel(c, b, level) : Call(c, b);
+        });
         check(r);
         w_.write(r.out[0].data(), r.out[0].size());
         buf_.clear();
         return std::move(w_);
     }
 private:
-    W w_; std::vector<uint8_t> buf_;
+    W w_; std::vector<uint8_t> buf_; int level_ = 0;
 };
 }  // namespace detail
 namespace flate {
-template <class W> using Encoder = detail::OneShotEncoder<W, rcx_deflate_encode_batch, 0>;   // one raw DEFLATE stream (RFC 1951)
+template <class W> using Encoder = detail::OneShotEncoder<W, rcx_deflate_encode_batch, rcx_deflate_encode_level_batch, 0>;   // one raw DEFLATE stream (RFC 1951)
 // many raw DEFLATE streams, ONE batch call (the reference decodes one deflate block per read(), flate.rs:468-488: a stream is one wave's work
 // on the GPU -- a caller with many streams hands them over together)
 inline detail::ManyResult decode_many(const std::vector<std::vector<uint8_t>>& streams)
@@ -478,7 +482,7 @@ public:
 };
 }  // namespace flate
 namespace zlib {
-template <class W> using Encoder = detail::OneShotEncoder<W, rcx_zlib_encode_batch, 6>;      // one zlib stream (RFC 1950)
+template <class W> using Encoder = detail::OneShotEncoder<W, rcx_zlib_encode_batch, rcx_zlib_encode_level_batch, 6>;      // one zlib stream (RFC 1950)
 inline detail::ManyResult decode_many(const std::vector<std::vector<uint8_t>>& members)      // every member's Adler-32 checked on the device
 { return detail::decode_many(members, [](rcx_ctx* c, rcx_batch* b, uint32_t* f) { return rcx_zlib_decode_batch(c, b, f); }); }
 template <class R>
