@@ -69,7 +69,62 @@ def encode(raws, fmt, level, caps=None, scratch_bytes=0, full=False):
     return rc, outs, st[:n], out_len[:n], in_used[:n]
 
 
+LAYOUT = ("link", "cand", "elen", "price", "pos", "seg_first", "seg_type", "seg_bits", "cap")
+# kernel launches of a raw DEFLATE encode at levels 2..9, in order (stop_after counts them): levels 7..9 price and parse twice
+LAUNCHES = ("plan", "links", "search", "price", "parse", "price2", "parse2")
+ALL = 0xFFFFFFFF
+
+
+def layout(base, nbytes, n):
+    """{array: byte offset} (and "cap": segments) of a level scratch of nbytes bytes at the address `base` for n streams, from the
+    kernels' own dh_carve."""
+    lay = np.zeros(len(LAYOUT), np.uint64)
+    lib().sim_deflate_hc_layout(C.c_uint64(base), C.c_uint64(nbytes), C.c_uint32(n), C.c_void_p(lay.ctypes.data))
+    return {k: int(v) for k, v in zip(LAYOUT, lay)}
+
+
+def scratch_bytes_for(n, segs):
+    f = lib().sim_deflate_hc_scratch_bytes
+    f.restype = C.c_uint64
+    return int(f(C.c_uint32(n), C.c_uint64(segs)))
+
+
+def stages(raws, level, stop_after=ALL, lead=0, fill=0xA5):
+    """A raw DEFLATE encode at `level` of which the first stop_after kernel launches run (LAUNCHES; ALL: the whole encode), in a
+    scratch filled with `fill`.  `lead` bytes of padding precede every stream in the input buffer.  -> (rc, outputs, status, scratch,
+    layout): the scratch as a uint8 array and layout(...) of it; tests/hc_stages.py cuts it into per-stream views."""
+    n = len(raws)
+    in_off = np.zeros(max(n, 1), np.uint64)
+    in_len = np.array([len(r) for r in raws] or [0], np.uint64)
+    buf = bytearray()
+    for i, r in enumerate(raws):
+        buf += b"\xC3" * lead
+        in_off[i] = len(buf)
+        buf += r
+    inb = np.frombuffer(bytes(buf) + b"\0" * 16, np.uint8).copy()
+    from rust_compress_amd import _native as N
+    caps = [int(N.lib().rcx_deflate_compression_bound(len(r))) for r in raws]
+    out_cap = np.array(caps or [0], np.uint64)
+    out_off = np.concatenate([[0], np.cumsum(out_cap)[:-1]]).astype(np.uint64)
+    out = np.full(int(out_cap.sum()) + 16, 0xEE, np.uint8)
+    out_len = np.zeros(max(n, 1), np.uint64)
+    in_used = np.zeros(max(n, 1), np.uint64)
+    st = np.full(max(n, 1), -1, np.int32)
+    sb = scratch_bytes_for(n, sum((len(r) + 65535) // 65536 for r in raws))
+    scratch = np.full(sb + 64, fill, np.uint8)
+    lay = np.zeros(len(LAYOUT), np.uint64)
+    P = lambda a: C.c_void_p(a.ctypes.data)
+    rc = lib().sim_deflate_hc_stages(0, level, P(inb), P(in_off), P(in_len), P(out), P(out_off), P(out_cap), P(out_len), P(in_used),
+                                     P(st), n, C.c_uint32(stop_after), P(scratch), C.c_uint64(sb), P(lay))
+    outs = [bytes(out[int(out_off[i]):int(out_off[i]) + int(out_len[i])]) for i in range(n)]
+    return rc, outs, st[:n], scratch, {k: int(v) for k, v in zip(LAYOUT, lay)}
+
+
 def _job(args):
+    """a job is encode's arguments, or ("stages", reduce, ...): reduce(raws, stages(...)) -- what the worker sends back (a function
+    of a module the workers can import), so that whole scratches do not travel between processes"""
+    if args and isinstance(args[0], str) and args[0] == "stages":
+        return args[1](args[2], stages(*args[2:]))
     return encode(*args)
 
 

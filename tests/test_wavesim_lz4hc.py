@@ -66,11 +66,30 @@ def _raws():
     return raws
 
 
-@pytest.mark.parametrize("level", [1, 9])
-def test_round_trip_and_block_format(oracle, level):
+KINDS = ("text", "words", "runs", "dna4")
+
+
+def _blocks(kind):
+    return [synth.gen(kind, 65536, s).tobytes() for s in range(100, 102)]
+
+
+@pytest.fixture(scope="module")
+def runs():
+    """the simulator runs the tests below share, spread over worker processes (the slowest first)"""
+    import sim_lz4hc_run
+    jobs = {}
+    for lv in (12, 10, 9, 4, 1):
+        jobs[("rt", lv)] = (_raws(), lv)
+    for lv in range(12, 0, -1):
+        jobs[("grow", lv)] = ([b for k in KINDS for b in _blocks(k)], lv)
+    return dict(zip(jobs, sim_lz4hc_run.encode_many(list(jobs.values()))))
+
+
+@pytest.mark.parametrize("level", [1, 4, 9, 10, 12])
+def test_round_trip_and_block_format(oracle, runs, level):
     import sim_lz4hc_run
     raws = _raws()
-    rc, outs, st, out_len, in_used, _, _ = sim_lz4hc_run.encode(raws, level)
+    rc, outs, st, out_len, in_used, _, _ = runs[("rt", level)]
     assert rc == 0 and not st.any()
     assert [int(u) for u in in_used] == [len(r) for r in raws]
     for r, e in zip(raws, outs):
@@ -80,6 +99,21 @@ def test_round_trip_and_block_format(oracle, level):
         assert len(e) <= 1 + len(r) + (1 + (len(r) - 15) // 255 if len(r) >= 15 else 0)    # never more than the block as literals
     # the long, compressible inputs use matches
     assert check_block(outs[-1], len(raws[-1]))[0] > 0 and check_block(outs[-2], len(raws[-2]))[0] > 0
+
+
+def test_levels_do_not_grow(oracle, runs):
+    """Total over two 64 KiB blocks of each kind: a level is at most 1.005 of the level below (the tolerance of the DEFLATE levels'
+    test: a deeper search changes the candidates, and the parse's cost of a literal run is not exact)."""
+    tot = []
+    for lv in range(1, 13):
+        rc, outs, st, _, _, _, _ = runs[("grow", lv)]
+        assert rc == 0 and not st.any()
+        tot.append(sum(map(len, outs)))
+    raws = [b for k in KINDS for b in _blocks(k)]
+    for r, e in zip(raws, runs[("grow", 12)][1]):
+        assert oracle.lz4_decode_block(e, cap=len(r)) == r
+    for k in range(11):
+        assert tot[k + 1] <= 1.005 * tot[k], tot
 
 
 def test_long_runs(oracle):
