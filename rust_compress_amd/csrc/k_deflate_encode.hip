@@ -33,7 +33,9 @@
 //                        from the segment's staging (or, for stored segments, from the input) and the next segment's first bits,
 //                        and stored: no word is written twice, and nothing but the stream's own bytes (no read-modify-write)
 // Workgroups never talk to each other inside a launch.  Scratch is carved in de_carve; nothing in it is assumed zero.
-#include "rcx_dev.h"
+// The segment list (plan body, owner search, segment descriptor), the prefix extension and the block-wide scan are lz_match.h's,
+// shared with k_lz4_hc.hip and k_deflate_hc.hip.
+#include "lz_match.h"
 #include "k_crc32.hip"                // rcx_crc_mulmod / rcx_crc_xpow: the per-segment CRC-32s joined per stream
 
 #define DE_SEG 65536u                  /* bytes per segment (one block) */
@@ -91,7 +93,6 @@ static inline DeScratch de_carve(void* scratch, uint64_t bytes, uint32_t n)
     return d;
 }
 
-__device__ __forceinline__ uint32_t de_ld32(const uint8_t* p) { return *(const rcx_u32_u*)p; }
 __device__ __forceinline__ uint32_t de_hash(uint32_t x) { return (x * 2654435761u) >> (32 - DE_HBITS); }
 __device__ __forceinline__ uint32_t de_rev(uint32_t c, uint32_t len) { return __brev(c) >> (32 - len); }
 
@@ -114,17 +115,6 @@ __device__ __forceinline__ void de_dist_sym(uint32_t d, uint32_t& sym, uint32_t&
     eb = k - 1;
     sym = 2 * k + ((dd >> (k - 1)) & 1u);
     ev = dd & ((1u << eb) - 1u);
-}
-// common prefix of in[p..] and in[q..], at most maxl bytes (in[p + maxl - 1] is the last byte read)
-__device__ __forceinline__ uint32_t de_extend(const uint8_t* in, uint32_t p, uint32_t q, uint32_t maxl)
-{
-    uint32_t l = 0;
-    for (;;) {
-        if (l + 4 > maxl) { while (l < maxl && in[p + l] == in[q + l]) l++; return l; }
-        const uint32_t x = de_ld32(in + p + l) ^ de_ld32(in + q + l);
-        if (x) return l + ((uint32_t)__builtin_ctz(x) >> 3);
-        l += 4;
-    }
 }
 __device__ __forceinline__ uint32_t de_fixed_llen(uint32_t s) { return s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8; }
 
@@ -207,65 +197,28 @@ __device__ void de_rank_sort(const uint32_t* freq, uint32_t nsym, uint16_t* sort
     }
 }
 
-__device__ uint32_t de_block_excl_scan(uint32_t v, uint32_t* s_ws, uint32_t& total)
-{
-    const uint32_t lane = rcx_lane(), wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t inc = v;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) s_ws[wv] = inc;
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-    for (uint32_t w = 0; w < nw; w++) { const uint32_t x = s_ws[w]; if (w < wv) off += x; tot += x; }
-    __syncthreads();
-    total = tot;
-    return off + inc - v;
-}
-
-// which stream a flattened segment belongs to: the last b with seg_first[b] <= g
-__device__ __forceinline__ uint32_t de_stream_of(const uint32_t* sf, uint32_t n, uint32_t g)
-{
-    uint32_t lo = 0, hi = n;                          // sf[lo] <= g < sf[hi]
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (sf[mid] <= g) lo = mid; else hi = mid; }
-    return lo;
-}
-
 __device__ __forceinline__ uint32_t de_nseg(uint64_t len) { return len >> 32 ? 0u : (uint32_t)((len + DE_SEG - 1) / DE_SEG); }
+
+__device__ __forceinline__ LzcSeg de_seg(const rcx_kargs& a, const DeScratch& d, uint32_t g) { return lzc_seg<DE_SEG>(a, d.seg_first, g); }
+__device__ __forceinline__ uint32_t de_lim(const rcx_kargs& a, const DeScratch& d) { return lzc_lim(a, d.seg_first, d.cap); }
 
 __global__ __launch_bounds__(1024) void k_de_plan(rcx_kargs a, DeScratch d)
 {
     __shared__ uint32_t s_ws[16];
     __shared__ uint32_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    const uint32_t n = a.nblocks;
-    for (uint32_t b0 = 0; b0 < n; b0 += blockDim.x) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t v = b < n ? de_nseg(a.in_len[b]) : 0u;
-        uint32_t tot;
-        const uint32_t ex = de_block_excl_scan(v, s_ws, tot);
-        const uint32_t c = s_carry;
-        if (b < n) d.seg_first[b] = c + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) s_carry = c + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) d.seg_first[n] = s_carry;
+    lzc_plan(a.nblocks, d.seg_first, s_ws, &s_carry, [&](uint32_t b) { return de_nseg(a.in_len[b]); });
 }
 
 // the flattened segments as blocks of input for the checksum kernels (entries past the last segment: empty blocks)
 __global__ __launch_bounds__(256) void k_de_segs(rcx_kargs a, DeScratch d)
 {
-    const uint32_t n = a.nblocks, total = d.seg_first[n];
+    const uint32_t total = d.seg_first[a.nblocks];
     for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < d.cap; g += gridDim.x * blockDim.x) {
         uint64_t o = 0, l = 0;
         if (g < total) {
-            const uint32_t b = de_stream_of(d.seg_first, n, g);
-            const uint64_t s0 = (uint64_t)(g - d.seg_first[b]) * DE_SEG, len = a.in_len[b];
-            o = a.in_off[b] + s0;
-            l = len - s0 < DE_SEG ? len - s0 : DE_SEG;
+            const LzcSeg s = de_seg(a, d, g);
+            o = a.in_off[s.b] + s.s0;
+            l = s.L;
         }
         d.seg_ioff[g] = o; d.seg_ilen[g] = l;
     }
@@ -296,7 +249,8 @@ __global__ __launch_bounds__(DE_T) void k_de_segment(rcx_kargs a, DeScratch d)
     const uint32_t lim = total < d.cap ? total : d.cap;
 
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
-        const uint32_t b = de_stream_of(d.seg_first, n, g);
+        // (lzc_seg's lines, written out: with de_seg(a, d, g) here this kernel compiled to 215 VGPRs and took 2-6 % longer)
+        const uint32_t b = lzc_owner_of(d.seg_first, n, g);
         const uint8_t* in = a.in_base + a.in_off[b];
         const uint32_t len = (uint32_t)a.in_len[b];
         const uint32_t s0 = (g - d.seg_first[b]) * DE_SEG;
@@ -316,7 +270,7 @@ __global__ __launch_bounds__(DE_T) void k_de_segment(rcx_kargs a, DeScratch d)
         const uint32_t ws0 = s0 > DE_WIN ? s0 - DE_WIN : 0;
         for (uint32_t r = tid; r < s0 - ws0; r += DE_T) {
             const uint32_t x = ws0 + r;
-            if (len - x >= 4) atomicMax(&s_big[de_hash(de_ld32(in + x))], x + 1);
+            if (len - x >= 4) atomicMax(&s_big[de_hash(lzc_ld32(in + x))], x + 1);
         }
         __syncthreads();
         // 2. the segment 512 positions a round: the table's candidate for every position, then the longest match among it, distance 1
@@ -327,10 +281,10 @@ __global__ __launch_bounds__(DE_T) void k_de_segment(rcx_kargs a, DeScratch d)
             uint32_t h = 0, dh = 0;
             const bool hashed = rel < L && len - p >= 4;
             if (hashed) {
-                const uint32_t x = de_ld32(in + p);
+                const uint32_t x = lzc_ld32(in + p);
                 h = de_hash(x);
                 const uint32_t q1 = s_big[h];
-                if (q1 && p - (q1 - 1) <= DE_WIN && de_ld32(in + q1 - 1) == x) dh = p - (q1 - 1);
+                if (q1 && p - (q1 - 1) <= DE_WIN && lzc_ld32(in + q1 - 1) == x) dh = p - (q1 - 1);
             }
             s_cd[8 + tid] = dh;
             __syncthreads();
@@ -345,7 +299,7 @@ __global__ __launch_bounds__(DE_T) void k_de_segment(rcx_kargs a, DeScratch d)
                     bool seen = false;
                     for (int j = 0; j < i; j++) seen |= cand[j] == dd;
                     if (seen) continue;
-                    const uint32_t l = de_extend(in, p, p - dd, maxl);
+                    const uint32_t l = lzc_extend(in, p, p - dd, maxl);
                     if (l > bl || (l == bl && dd < bd)) { bl = l; bd = dd; }
                 }
                 if (bl >= 5 || (bl == 4 && bd <= DE_FAR4)) m = (bl << 16) | (bd - 1);
@@ -532,7 +486,7 @@ __global__ __launch_bounds__(DE_T) void k_de_segment(rcx_kargs a, DeScratch d)
                 } else nb += ll[in[s0 + p]];
             }
             uint32_t tot;
-            const uint32_t off = de_block_excl_scan(nb, s_ws, tot) + s_x[4];
+            const uint32_t off = lzc_block_excl_scan(nb, s_ws, tot) + s_x[4];
             DeBits w; w.start(s_big, off);
             for (uint32_t p = r0; p < r1; p++) {
                 if (var == 0 && !((s_start[p >> 6] >> (p & 63)) & 1ull)) continue;
@@ -712,16 +666,15 @@ __device__ __forceinline__ uint32_t de_seg_bits32(const DeScratch& d, const uint
 template <int FMT>
 __global__ __launch_bounds__(256) void k_de_place(rcx_kargs a, DeScratch d)
 {
-    const uint32_t n = a.nblocks;
-    const uint32_t total = d.seg_first[n];
-    const uint32_t lim = total < d.cap ? total : d.cap;
+    const uint32_t lim = de_lim(a, d);
     const uint32_t HDR = FMT == DE_ZLIB ? 2 : FMT == DE_GZIP ? 10 : 0;
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
-        const uint32_t b = de_stream_of(d.seg_first, n, g);
+        const LzcSeg s = de_seg(a, d, g);
+        const uint32_t b = s.b;
         if (!d.sflag[b]) continue;
-        const uint32_t f0 = d.seg_first[b], f1 = d.seg_first[b + 1];
-        const uint8_t* in = a.in_base + a.in_off[b];
-        const uint64_t len = a.in_len[b];
+        const uint32_t f0 = s.f0, f1 = d.seg_first[b + 1];
+        const uint8_t* in = s.in;
+        const uint64_t len = s.len;                                        // (a stream that has segments is shorter than 2^32)
         const bool last = g + 1 == f1;
         const uint64_t o0 = d.seg_off[g], o1 = o0 + d.seg_bits[g];
         const uint64_t dbytes = a.out_len[b] - HDR - (FMT == DE_ZLIB ? 4 : FMT == DE_GZIP ? 8 : 0);

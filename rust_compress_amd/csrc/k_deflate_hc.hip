@@ -6,13 +6,12 @@
 // builds each block as k_de_segment does (dh_block, a copy of its phases 3-7: histograms, trees, the cheapest block type by exact bit
 // count, the packed bits).  Only the per-segment parse is new.  Launches, in stream order (the ones of k_deflate_encode.hip in brackets):
 //   [k_de_plan, k_de_segs + k_adler32 / k_crc32]
-//   k_dh_links   a workgroup per segment: exact hash chains over the 32 KiB before the segment and the segment itself.  A 2^15-bucket
-//                table of 4-byte prefixes in LDS is filled with the window (atomicMax: the latest position per bucket), then one wave
-//                walks the segment 64 positions at a time: a position's link is the distance to the nearest earlier position of its
-//                bucket (inside the 64 from the hashes staged in LDS, else the table), 0 = none within 32768.  16-bit links, indexed
-//                by the stream's first segment * DE_SEG + position in the stream, so the window's links are the previous segment's
+//   k_dh_links   a workgroup per segment: exact hash chains over the 32 KiB before the segment and the segment itself (lzc_links of
+//                lz_match.h, shared with LZ4 HC): 16-bit links, 0 = none within 32768, indexed by the stream's first segment *
+//                DE_SEG + position in the stream, so the window's links are the previous segment's
 //   k_dh_search  a workgroup per segment: every position walks its chain up to the level's depth and keeps the longest match (the
-//                nearest among equals) of at least 4 bytes, at most 258 and not past the segment's end; it stops at a 258-byte match
+//                nearest among equals; lzc_search) of at least 4 bytes, at most 258 and not past the segment's end; it stops at a
+//                258-byte match
 //   k_dh_price   a workgroup per segment: a parse walked from the segment's start (the greedy one over the longest matches, or the
 //                previous min-cost parse), its literal/length and distance histograms, and from them code lengths (15 bits at most)
 //                of frequencies 8 f + 1 -- every symbol gets a price, the unseen ones a high one
@@ -29,8 +28,6 @@
 // The output is deterministic: no step depends on the order in which threads or workgroups run (atomicMax / atomicMin pick the same
 // entry in any order).  Scratch is carved in dh_carve; nothing in it is assumed zero.
 
-#define DH_HBITS 15
-#define DH_CHUNK 8192u                 /* hashes staged in LDS at a time by k_dh_links */
 #define DH_RING 512u                   /* k_dh_parse's ring of long-match arrivals (> 63 + 258 positions ahead) */
 #define DH_ELEN (DE_SEG + 64u)         /* per-segment entries of the parse's arrival record (positions 0..L) */
 #define DH_INF 0xffffffffu
@@ -69,29 +66,9 @@ static inline DeScratch dh_carve(void* scratch, uint64_t bytes, uint32_t n, DhSc
     return d;
 }
 
-__device__ __forceinline__ uint32_t dh_hash(uint32_t x) { return (x * 2654435761u) >> (32 - DH_HBITS); }
-
-// the segment g of stream b: its start in the stream and its length
-struct DhSeg { uint32_t f0, s0, L, len; const uint8_t* in; };
-__device__ __forceinline__ DhSeg dh_seg(const rcx_kargs& a, const DeScratch& d, uint32_t g)
-{
-    DhSeg s;
-    const uint32_t b = de_stream_of(d.seg_first, a.nblocks, g);
-    s.f0 = d.seg_first[b];
-    s.in = a.in_base + a.in_off[b];
-    s.len = (uint32_t)a.in_len[b];
-    s.s0 = (g - s.f0) * DE_SEG;
-    s.L = s.len - s.s0 < DE_SEG ? s.len - s.s0 : DE_SEG;
-    return s;
-}
-__device__ __forceinline__ uint32_t dh_lim(const rcx_kargs& a, const DeScratch& d)
-{
-    const uint32_t total = d.seg_first[a.nblocks];
-    return total < d.cap ? total : d.cap;
-}
-
-// k_dh_block's LDS and block builder: phases 3-7 of k_de_segment, copied.  (Factored into one __device__ function that both kernels
-// called, k_de_segment compiled to different code and took 2.6-11 % longer on an MI355X; so it keeps its own.)
+// k_dh_block's LDS and block builder: phases 3-7 of k_de_segment, copied -- a fix to one must be made in the other.  (Factored into
+// one __device__ function that both kernels called, in two forms, k_de_segment compiled to different code and took 1.7-11 % longer on
+// an MI355X; so it keeps its own.  DESIGN 3.12 has the forms and their times.)
 struct DhLds {
     uint32_t big[DE_BIGW];                                // hash table (phases 1-2), then the packed block (phase 7)
     uint64_t start[DE_SEG / 64];                          // token starts of the parse
@@ -309,7 +286,7 @@ __device__ __forceinline__ void dh_block(DhLds& S, const DeScratch& d, uint32_t 
             } else nb += ll[in[s0 + p]];
         }
         uint32_t tot;
-        const uint32_t off = de_block_excl_scan(nb, s_ws, tot) + s_x[4];
+        const uint32_t off = lzc_block_excl_scan(nb, s_ws, tot) + s_x[4];
         DeBits w; w.start(s_big, off);
         for (uint32_t p = r0; p < r1; p++) {
             if (var == 0 && !((s_start[p >> 6] >> (p & 63)) & 1ull)) continue;
@@ -338,76 +315,28 @@ __device__ __forceinline__ void dh_block(DhLds& S, const DeScratch& d, uint32_t 
 
 __global__ __launch_bounds__(256) void k_dh_links(rcx_kargs a, DeScratch d, DhScratch h)
 {
-    __shared__ uint32_t s_head[1u << DH_HBITS];
-    __shared__ uint16_t s_hc[DH_CHUNK];                   // the chunk's hashes (0xffff: fewer than 4 bytes left in the stream)
-    const uint32_t tid = threadIdx.x, lane = rcx_lane();
-    const uint32_t lim = dh_lim(a, d);
+    __shared__ uint32_t s_head[1u << LZC_HBITS];
+    __shared__ uint16_t s_hc[LZC_CHUNK];
+    const uint32_t lim = de_lim(a, d);
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
-        const DhSeg s = dh_seg(a, d, g);
-        uint16_t* link = h.link + (uint64_t)s.f0 * DE_SEG;
-        for (uint32_t i = tid; i < (1u << DH_HBITS); i += blockDim.x) s_head[i] = 0;
-        __syncthreads();
-        const uint32_t h0 = s.s0 > DE_WIN ? s.s0 - DE_WIN : 0;
-        for (uint32_t x = h0 + tid; x < s.s0; x += blockDim.x)
-            if (s.len - x >= 4) atomicMax(&s_head[dh_hash(de_ld32(s.in + x))], x + 1);
-        __syncthreads();
-        for (uint32_t c0 = 0; c0 < s.L; c0 += DH_CHUNK) {
-            const uint32_t cn = s.L - c0 < DH_CHUNK ? s.L - c0 : DH_CHUNK;
-            for (uint32_t i = tid; i < cn; i += blockDim.x) {
-                const uint32_t p = s.s0 + c0 + i;
-                s_hc[i] = s.len - p >= 4 ? (uint16_t)dh_hash(de_ld32(s.in + p)) : (uint16_t)0xffffu;
-            }
-            __syncthreads();
-            if (tid < 64) {
-                for (uint32_t r0 = 0; r0 < cn; r0 += 64) {
-                    const uint32_t i = r0 + lane, p = s.s0 + c0 + i;
-                    const bool live = i < cn;
-                    const uint32_t hv = live ? s_hc[i] : 0xffffu;
-                    uint32_t lk = 0;
-                    if (hv != 0xffffu) {
-                        for (uint32_t j = i; j > r0; j--) if (s_hc[j - 1] == hv) { lk = i - (j - 1); break; }
-                        if (!lk) {
-                            const uint32_t q = s_head[hv];
-                            if (q && p - (q - 1) <= DE_WIN) lk = p - (q - 1);
-                        }
-                    }
-                    if (live) link[p] = (uint16_t)lk;
-                    __builtin_amdgcn_wave_barrier();
-                    if (hv != 0xffffu) atomicMax(&s_head[hv], p + 1);
-                    __builtin_amdgcn_wave_barrier();
-                }
-            }
-            __syncthreads();
-        }
+        const LzcSeg s = de_seg(a, d, g);
+        lzc_links<DE_WIN>(s, h.link + (uint64_t)s.f0 * DE_SEG, s_head, s_hc);
     }
 }
 
+// DEFLATE's matches: at most 258 bytes and not past the segment's end (its block); the distance is stored less one
+struct DhMatch {
+    static constexpr uint32_t WIN = DE_WIN;
+    static __device__ __forceinline__ uint32_t maxl(const LzcSeg& s, uint32_t i) { return s.L - i < 258 ? s.L - i : 258; }
+    static __device__ __forceinline__ uint32_t pack(uint32_t len, uint32_t dist) { return (len << 16) | (dist - 1); }
+};
+
 __global__ __launch_bounds__(256) void k_dh_search(rcx_kargs a, DeScratch d, DhScratch h, uint32_t depth)
 {
-    const uint32_t lim = dh_lim(a, d);
+    const uint32_t lim = de_lim(a, d);
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
-        const DhSeg s = dh_seg(a, d, g);
-        const uint16_t* link = h.link + (uint64_t)s.f0 * DE_SEG;
-        uint32_t* cand = h.cand + (uint64_t)g * DE_SEG;
-        for (uint32_t i = threadIdx.x; i < s.L; i += blockDim.x) {
-            const uint32_t p = s.s0 + i;
-            const uint32_t maxl = s.L - i < 258 ? s.L - i : 258;         // (the match ends inside the segment: its block)
-            uint32_t best = 0, bd = 0;
-            if (maxl >= 4) {
-                uint32_t dist = 0;
-                for (uint32_t k = 0; k < depth; k++) {
-                    const uint32_t lk = link[p - dist];
-                    if (!lk) break;
-                    dist += lk;
-                    if (dist > DE_WIN) break;
-                    const uint32_t q = p - dist;
-                    if (best >= 4 && s.in[q + best] != s.in[p + best]) continue;
-                    const uint32_t l = de_extend(s.in, p, q, maxl);
-                    if (l > best) { best = l; bd = dist; if (best == maxl) break; }
-                }
-            }
-            cand[i] = best >= 4 ? (best << 16) | (bd - 1) : 0u;
-        }
+        const LzcSeg s = de_seg(a, d, g);
+        lzc_search<DhMatch>(s, h.link + (uint64_t)s.f0 * DE_SEG, h.cand + (uint64_t)g * DE_SEG, depth);
     }
 }
 
@@ -420,9 +349,9 @@ __global__ __launch_bounds__(DE_T) void k_dh_price(rcx_kargs a, DeScratch d, DhS
     __shared__ uint16_t s_sort[288 + 32];
     __shared__ uint8_t s_len[288 + 32];
     const uint32_t tid = threadIdx.x;
-    const uint32_t lim = dh_lim(a, d);
+    const uint32_t lim = de_lim(a, d);
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
-        const DhSeg s = dh_seg(a, d, g);
+        const LzcSeg s = de_seg(a, d, g);
         const uint32_t* src = (from_parse ? d.pos : h.cand) + (uint64_t)g * DE_SEG;
         for (uint32_t i = tid; i < 288 + 32; i += DE_T) { s_f[i] = 0; s_len[i] = 0; }
         __syncthreads();
@@ -464,9 +393,9 @@ __global__ __launch_bounds__(64) void k_dh_parse(rcx_kargs a, DeScratch d, DhScr
     __shared__ uint16_t s_lc[259];                        // bits of a match length: its code + extra bits
     __shared__ uint8_t s_lit[256], s_dl[32];
     const uint32_t lane = rcx_lane();
-    const uint32_t lim = dh_lim(a, d);
+    const uint32_t lim = de_lim(a, d);
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
-        const DhSeg s = dh_seg(a, d, g);
+        const LzcSeg s = de_seg(a, d, g);
         const uint32_t L = s.L;
         const uint8_t* in = s.in + s.s0;
         const uint32_t* cand = h.cand + (uint64_t)g * DE_SEG;
@@ -553,9 +482,9 @@ __global__ __launch_bounds__(DE_T) void k_dh_block(rcx_kargs a, DeScratch d)
 {
     __shared__ DhLds S;
     const uint32_t tid = threadIdx.x;
-    const uint32_t lim = dh_lim(a, d);
+    const uint32_t lim = de_lim(a, d);
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
-        const DhSeg s = dh_seg(a, d, g);
+        const LzcSeg s = de_seg(a, d, g);
         for (uint32_t i = tid; i < 288; i += DE_T) S.lf[i] = 0;
         if (tid < 32) S.df[tid] = 0;
         if (tid < 24) S.x[tid] = 0;

@@ -8,13 +8,11 @@
 // Segment-parallel, as k_deflate_encode.hip.  Every block is cut into HC_SEG-byte segments, the segments of the batch are flattened;
 // matches reach back up to 65535 bytes, across segment boundaries; a segment's parse ends at the segment's end.  Launches:
 //   k_hc_plan    one workgroup: exclusive scan of the blocks' segment counts (0 for a block that gets a status of its own)
-//   k_hc_links   a workgroup per segment: exact hash chains.  A 2^15-bucket table of 4-byte prefixes in LDS (position + 1) is filled
-//                with the 65535 bytes before the segment (atomicMax: the latest position per bucket, order-free), then one wave walks
-//                the segment 64 positions at a time: a position's link is the distance to the nearest earlier position of its bucket
-//                (inside the 64 from the hashes staged in LDS, else the table), 0 = none within 65535.  Links are 16-bit, per position
+//   k_hc_links   a workgroup per segment: exact hash chains over the 65535 bytes before the segment and the segment (lzc_links of
+//                lz_match.h, shared with DEFLATE's levels 2..9): 16-bit links, per position, 0 = none within 65535
 //   k_hc_search  a workgroup per segment: every position walks its chain up to the level's depth and keeps the longest match
-//                (the nearest among equals), at most HC_MAXM bytes, ending at least 5 bytes before the block's end and starting at
-//                least 12 bytes before it
+//                (the nearest among equals; lzc_search), at most HC_MAXM bytes, ending at least 5 bytes before the block's end and
+//                starting at least 12 bytes before it
 //   k_hc_parse   a wave per segment: forward min-cost parse.  The cheapest way to reach each position is relaxed in a 64-position
 //                register ring (lane = position mod 64; a literal costs 1 byte plus the length byte its run needs at 15, 270, ...;
 //                a match of length 4..min(L, 63) 3 bytes plus its length bytes), matches of 64 bytes or more through a 2048-entry LDS
@@ -26,12 +24,10 @@
 //   k_hc_place   a workgroup per segment: the tokens (a thread per run of tokens, offsets from a block-wide scan), the literals before
 //                the first and after the last match (the whole workgroup), the final token's header (the block's last segment)
 // Scratch is carved in hc_carve; nothing in it is assumed zero.  Workgroups never talk to each other inside a launch.
-#include "rcx_dev.h"
+#include "lz_match.h"
 
 #define HC_SEG 65536u                  /* bytes per segment */
 #define HC_WIN 65535u                  /* largest LZ4 offset */
-#define HC_HBITS 15
-#define HC_CHUNK 8192u                 /* hashes staged in LDS at a time by k_hc_links */
 #define HC_RING 2048u                  /* k_hc_parse's ring of long-match arrivals */
 #define HC_MAXM (HC_RING - 64u)        /* longest match the search reports and the parse relaxes (the parse's walk joins adjacent pieces of one run) */
 #define HC_TOKCAP 16384u               /* matches a segment can hold (each is >= 4 bytes) */
@@ -97,165 +93,56 @@ static inline HcScratch hc_carve(void* scratch, uint64_t bytes, uint32_t n)
     return d;
 }
 
-__device__ __forceinline__ uint32_t hc_ld32(const uint8_t* p) { return *(const rcx_u32_u*)p; }
-__device__ __forceinline__ uint32_t hc_hash(uint32_t x) { return (x * 2654435761u) >> (32 - HC_HBITS); }
 // length bytes of a literal run / of a match of length l (the token's nibble holds 0..14, then 255s and a remainder byte)
 __host__ __device__ __forceinline__ uint64_t hc_lext(uint64_t r) { return r >= 15 ? 1 + (r - 15) / 255 : 0; }
 __device__ __forceinline__ uint32_t hc_mext(uint32_t l) { return l >= 19 ? 1 + (l - 19) / 255 : 0; }
-// common prefix of in[p..] and in[q..], at most maxl bytes (in[p + maxl - 1] is the last byte read)
-__device__ __forceinline__ uint32_t hc_extend(const uint8_t* in, uint32_t p, uint32_t q, uint32_t maxl)
-{
-    uint32_t l = 0;
-    for (;;) {
-        if (l + 4 > maxl) { while (l < maxl && in[p + l] == in[q + l]) l++; return l; }
-        const uint32_t x = hc_ld32(in + p + l) ^ hc_ld32(in + q + l);
-        if (x) return l + ((uint32_t)__builtin_ctz(x) >> 3);
-        l += 4;
-    }
-}
 
-__device__ uint32_t hc_block_excl_scan(uint32_t v, uint32_t* s_ws, uint32_t& total)
-{
-    const uint32_t lane = rcx_lane(), wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t inc = v;
-    for (uint32_t dd = 1; dd < 64; dd <<= 1) {
-        const uint32_t t = __shfl_up(inc, dd);
-        if (lane >= dd) inc += t;
-    }
-    if (lane == 63) s_ws[wv] = inc;
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-    for (uint32_t w = 0; w < nw; w++) { const uint32_t x = s_ws[w]; if (w < wv) off += x; tot += x; }
-    __syncthreads();
-    total = tot;
-    return off + inc - v;
-}
-
-// which block a flattened segment belongs to: the last b with seg_first[b] <= g
-__device__ __forceinline__ uint32_t hc_block_of(const uint32_t* sf, uint32_t n, uint32_t g)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (sf[mid] <= g) lo = mid; else hi = mid; }
-    return lo;
-}
-
-// a block the segments work on: not too large for LZ4 and a slot of at least the compression bound (else its status says why)
-__device__ __forceinline__ bool hc_block_ok(const rcx_kargs& a, uint32_t b)
+// why a block gets a status of its own and no segments: too large for LZ4, or a slot smaller than the compression bound
+__device__ __forceinline__ int hc_block_status(const rcx_kargs& a, uint32_t b)
 {
     const uint64_t len = a.in_len[b];
-    return len <= 0x7e000000ull && a.out_cap[b] >= len + len / 255 + 20;
+    return len > 0x7e000000ull ? RCX_E_LZ4_INPUT_TOO_LARGE : a.out_cap[b] < len + len / 255 + 20 ? RCX_E_OUTPUT_TOO_SMALL : RCX_OK;
 }
+
+__device__ __forceinline__ LzcSeg hc_seg(const rcx_kargs& a, const HcScratch& d, uint32_t g) { return lzc_seg<HC_SEG>(a, d.seg_first, g); }
+__device__ __forceinline__ uint32_t hc_lim(const rcx_kargs& a, const HcScratch& d) { return lzc_lim(a, d.seg_first, d.cap); }
 
 __global__ __launch_bounds__(1024) void k_hc_plan(rcx_kargs a, HcScratch d)
 {
     __shared__ uint32_t s_ws[16];
     __shared__ uint32_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    const uint32_t n = a.nblocks;
-    for (uint32_t b0 = 0; b0 < n; b0 += blockDim.x) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t v = b < n && hc_block_ok(a, b) ? (uint32_t)hc_segments(a.in_len[b]) : 0u;
-        uint32_t tot;
-        const uint32_t ex = hc_block_excl_scan(v, s_ws, tot);
-        const uint32_t c = s_carry;
-        if (b < n) d.seg_first[b] = c + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) s_carry = c + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) d.seg_first[n] = s_carry;
-}
-
-// the segment g of block b: its start in the block and its length
-struct HcSeg { uint32_t b, f0, s0, L, len; const uint8_t* in; };
-__device__ __forceinline__ HcSeg hc_seg(const rcx_kargs& a, const HcScratch& d, uint32_t g)
-{
-    HcSeg s;
-    s.b = hc_block_of(d.seg_first, a.nblocks, g);
-    s.f0 = d.seg_first[s.b];
-    s.in = a.in_base + a.in_off[s.b];
-    s.len = (uint32_t)a.in_len[s.b];
-    s.s0 = (g - s.f0) * HC_SEG;
-    s.L = s.len - s.s0 < HC_SEG ? s.len - s.s0 : HC_SEG;
-    return s;
+    lzc_plan(a.nblocks, d.seg_first, s_ws, &s_carry,
+             [&](uint32_t b) { return hc_block_status(a, b) == RCX_OK ? (uint32_t)hc_segments(a.in_len[b]) : 0u; });
 }
 
 __global__ __launch_bounds__(256) void k_hc_links(rcx_kargs a, HcScratch d)
 {
-    __shared__ uint32_t s_head[1u << HC_HBITS];
-    __shared__ uint16_t s_hc[HC_CHUNK];                   // the chunk's hashes (0xffff: fewer than 4 bytes left in the block)
-    const uint32_t tid = threadIdx.x, lane = rcx_lane();
-    const uint32_t total = d.seg_first[a.nblocks];
-    const uint32_t lim = total < d.cap ? total : d.cap;
+    __shared__ uint32_t s_head[1u << LZC_HBITS];
+    __shared__ uint16_t s_hc[LZC_CHUNK];
+    const uint32_t lim = hc_lim(a, d);
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
-        const HcSeg s = hc_seg(a, d, g);
-        uint16_t* link = d.link + (uint64_t)s.f0 * HC_SEG;
-        for (uint32_t i = tid; i < (1u << HC_HBITS); i += blockDim.x) s_head[i] = 0;
-        __syncthreads();
-        const uint32_t h0 = s.s0 > HC_WIN ? s.s0 - HC_WIN : 0;
-        for (uint32_t x = h0 + tid; x < s.s0; x += blockDim.x)
-            if (s.len - x >= 4) atomicMax(&s_head[hc_hash(hc_ld32(s.in + x))], x + 1);
-        __syncthreads();
-        for (uint32_t c0 = 0; c0 < s.L; c0 += HC_CHUNK) {
-            const uint32_t cn = s.L - c0 < HC_CHUNK ? s.L - c0 : HC_CHUNK;
-            for (uint32_t i = tid; i < cn; i += blockDim.x) {
-                const uint32_t p = s.s0 + c0 + i;
-                s_hc[i] = s.len - p >= 4 ? (uint16_t)hc_hash(hc_ld32(s.in + p)) : (uint16_t)0xffffu;
-            }
-            __syncthreads();
-            if (tid < 64) {
-                for (uint32_t r0 = 0; r0 < cn; r0 += 64) {
-                    const uint32_t i = r0 + lane, p = s.s0 + c0 + i;
-                    const bool live = i < cn;
-                    const uint32_t h = live ? s_hc[i] : 0xffffu;
-                    uint32_t lk = 0;
-                    if (h != 0xffffu) {
-                        for (uint32_t j = i; j > r0; j--) if (s_hc[j - 1] == h) { lk = i - (j - 1); break; }
-                        if (!lk) {
-                            const uint32_t q = s_head[h];
-                            if (q && p - (q - 1) <= HC_WIN) lk = p - (q - 1);
-                        }
-                    }
-                    if (live) link[p] = (uint16_t)lk;
-                    __builtin_amdgcn_wave_barrier();
-                    if (h != 0xffffu) atomicMax(&s_head[h], p + 1);
-                    __builtin_amdgcn_wave_barrier();
-                }
-            }
-            __syncthreads();
-        }
+        const LzcSeg s = hc_seg(a, d, g);
+        lzc_links<HC_WIN>(s, d.link + (uint64_t)s.f0 * HC_SEG, s_head, s_hc);
     }
 }
 
+// LZ4's matches: at most HC_MAXM bytes, the last one starts 12 bytes before the block's end at the latest and ends 5 bytes before it
+struct HcMatch {
+    static constexpr uint32_t WIN = HC_WIN;
+    static __device__ __forceinline__ uint32_t maxl(const LzcSeg& s, uint32_t i)
+    {
+        const uint32_t left = s.len - s.s0 - i;
+        return left < 12 ? 0u : left - 5 < HC_MAXM ? left - 5 : HC_MAXM;
+    }
+    static __device__ __forceinline__ uint32_t pack(uint32_t len, uint32_t dist) { return (len << 16) | dist; }
+};
+
 __global__ __launch_bounds__(256) void k_hc_search(rcx_kargs a, HcScratch d, uint32_t depth)
 {
-    const uint32_t total = d.seg_first[a.nblocks];
-    const uint32_t lim = total < d.cap ? total : d.cap;
+    const uint32_t lim = hc_lim(a, d);
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
-        const HcSeg s = hc_seg(a, d, g);
-        const uint16_t* link = d.link + (uint64_t)s.f0 * HC_SEG;
-        uint32_t* cand = d.cand + (uint64_t)g * HC_SEG;
-        for (uint32_t i = threadIdx.x; i < s.L; i += blockDim.x) {
-            const uint32_t p = s.s0 + i;
-            uint32_t best = 0, bd = 0;
-            if (s.len - p >= 12) {                                  // the last match starts 12 bytes before the end at the latest ...
-                const uint32_t room = s.len - 5 - p;                // ... and ends 5 bytes before it
-                const uint32_t maxl = room < HC_MAXM ? room : HC_MAXM;
-                uint32_t dist = 0;
-                for (uint32_t k = 0; k < depth; k++) {
-                    const uint32_t lk = link[p - dist];
-                    if (!lk) break;
-                    dist += lk;
-                    if (dist > HC_WIN) break;
-                    const uint32_t q = p - dist;
-                    if (best >= 4 && s.in[q + best] != s.in[p + best]) continue;
-                    const uint32_t l = hc_extend(s.in, p, q, maxl);
-                    if (l > best) { best = l; bd = dist; if (best == maxl) break; }
-                }
-            }
-            cand[i] = best >= 4 ? (best << 16) | bd : 0u;
-        }
+        const LzcSeg s = hc_seg(a, d, g);
+        lzc_search<HcMatch>(s, d.link + (uint64_t)s.f0 * HC_SEG, d.cand + (uint64_t)g * HC_SEG, depth);
     }
 }
 
@@ -264,10 +151,9 @@ __global__ __launch_bounds__(64) void k_hc_parse(rcx_kargs a, HcScratch d)
 {
     __shared__ uint64_t s_far[HC_RING];                   // arrivals of matches of 64 bytes or more: key << 32 | distance
     const uint32_t lane = rcx_lane();
-    const uint32_t total = d.seg_first[a.nblocks];
-    const uint32_t lim = total < d.cap ? total : d.cap;
+    const uint32_t lim = hc_lim(a, d);
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
-        const HcSeg s = hc_seg(a, d, g);
+        const LzcSeg s = hc_seg(a, d, g);
         const uint32_t L = s.L;
         uint32_t* cand = d.cand + (uint64_t)g * HC_SEG;
         uint32_t* elen = d.elen + (uint64_t)g * HC_ELEN;
@@ -357,9 +243,7 @@ __global__ __launch_bounds__(64) void k_hc_scan(rcx_kargs a, HcScratch d)
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.nblocks) return;
     const uint64_t len = a.in_len[b];
-    int st = RCX_OK;
-    if (len > 0x7e000000ull) st = RCX_E_LZ4_INPUT_TOO_LARGE;
-    else if (a.out_cap[b] < len + len / 255 + 20) st = RCX_E_OUTPUT_TOO_SMALL;
+    int st = hc_block_status(a, b);
     const uint32_t f0 = d.seg_first[b], f1 = d.seg_first[b + 1];
     if (!st && f1 > d.cap) st = RCX_E_MALFORMED;                      // scratch smaller than rcx_lz4_hc_scratch_bytes asked for
     uint64_t total = 0;
@@ -409,10 +293,9 @@ __global__ __launch_bounds__(256) void k_hc_place(rcx_kargs a, HcScratch d)
 {
     __shared__ uint32_t s_ws[8];
     const uint32_t tid = threadIdx.x;
-    const uint32_t total = d.seg_first[a.nblocks];
-    const uint32_t lim = total < d.cap ? total : d.cap;
+    const uint32_t lim = hc_lim(a, d);
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
-        const HcSeg s = hc_seg(a, d, g);
+        const LzcSeg s = hc_seg(a, d, g);
         const uint32_t flag = d.sflag[s.b];
         if (!flag) continue;                                               // (uniform: the whole workgroup moves on)
         uint8_t* out = a.out_base + a.out_off[s.b];
@@ -431,7 +314,7 @@ __global__ __launch_bounds__(256) void k_hc_place(rcx_kargs a, HcScratch d)
                 sz += 3 + r + hc_lext(r) + hc_mext(l);
             }
             uint32_t tot;
-            uint64_t o = d.seg_o[g] + hc_block_excl_scan((uint32_t)sz, s_ws, tot);    // (a segment's tokens: < 2^32 bytes, the first one's literals aside)
+            uint64_t o = d.seg_o[g] + lzc_block_excl_scan((uint32_t)sz, s_ws, tot);    // (a segment's tokens: < 2^32 bytes, the first one's literals aside)
             for (uint32_t k = k0; k < k1; k++) {
                 const uint64_t t = tok[k];
                 const uint32_t m = (uint32_t)t & 0xffffu, l = (uint32_t)(t >> 16) & 0xffffu, dist = (uint32_t)(t >> 32);

@@ -17,7 +17,7 @@ def build():
     ws = os.path.join(HERE, "wavesim")
     csrc = os.path.join(ROOT, "rust_compress_amd", "csrc")
     deps = [src, os.path.join(ws, "wavesim.h"), os.path.join(ws, "wavesim.cpp"), os.path.join(csrc, "k_deflate_encode.hip"),
-            os.path.join(csrc, "k_deflate_hc.hip"), os.path.join(csrc, "rcx_dev.h")]
+            os.path.join(csrc, "k_deflate_hc.hip"), os.path.join(csrc, "lz_match.h"), os.path.join(csrc, "rcx_dev.h")]
     if os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in deps):
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)

@@ -15,7 +15,8 @@ def build():
     src = os.path.join(HERE, "sim_deflate", "sim_deflate.cpp")
     ws = os.path.join(HERE, "wavesim")
     deps = [src, os.path.join(ws, "wavesim.h"), os.path.join(ws, "wavesim.cpp"),
-            os.path.join(ROOT, "rust_compress_amd", "csrc", "k_deflate_encode.hip"), os.path.join(ROOT, "rust_compress_amd", "csrc", "rcx_dev.h")]
+            os.path.join(ROOT, "rust_compress_amd", "csrc", "k_deflate_encode.hip"), os.path.join(ROOT, "rust_compress_amd", "csrc", "lz_match.h"),
+            os.path.join(ROOT, "rust_compress_amd", "csrc", "rcx_dev.h")]
     if os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in deps):
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
