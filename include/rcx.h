@@ -71,6 +71,8 @@ enum rcx_status {
     RCX_E_LZ4_VERSION = 41,
     /* lz4.rs:229-230: compression_bound() == None -> encode returns 0 */
     RCX_E_LZ4_INPUT_TOO_LARGE = 42,
+    /* rcx_lz4_decode_linked_batch: an earlier block of this block's chain failed, so its history does not exist */
+    RCX_E_LZ4_HISTORY = 43,
     /* gzip member framing (RFC 1952; extension, see rcx_gzip_decode_batch) */
     RCX_E_GZIP_MAGIC = 50,          /* ID1 ID2 != 1f 8b */
     RCX_E_GZIP_METHOD = 51,         /* CM != 8 */
@@ -157,6 +159,30 @@ uint64_t rcx_lz4_compression_bound(uint64_t in_len);
  * blocks it does not cover get RCX_E_MALFORMED. */
 int rcx_lz4_encode_hc_batch(rcx_ctx*, const rcx_batch*, int level);
 uint64_t rcx_lz4_hc_scratch_bytes(uint32_t nblocks, uint64_t max_block);
+
+/* ---- extension beyond the reference: the LZ4 frame format's two device capabilities (lz4_Frame_format.md; the reference's frame
+ * types skip every checksum and break on dependent blocks).  rust_compress_amd/lz4frame.py builds conforming frames on them.
+ * XXH32 (the frame format's header, block and content checksum) of every block: hash[i] = XXH32(block i, seed); out_base, out_off,
+ * out_cap and out_len are unused, in_used[i] = in_len[i].  Any length up to 2^32 - 1 and any alignment of in_off.  A stream is a serial
+ * chain (the round does not combine across chunks the way CRC-32 and Adler-32 do): the rate comes from the batch.  Measured on MI355X,
+ * device memory: 4096 x 64 KiB in 0.151 ms a call (1659 GiB/s), one 256 MiB stream 368.7 ms (0.68 GiB/s). */
+int rcx_xxh32_batch(rcx_ctx*, const rcx_batch*, uint32_t seed, uint32_t* hash);
+/* LZ4 block decode with HISTORY: linked blocks and dictionaries.  link and dict_len are host arrays of nblocks entries, or NULL (= all 0).
+ *   link[i] == 0, a chain head: block i decodes into its slot as in rcx_lz4_decode_batch, and its matches may also reach into the
+ *     dict_len[i] (at most 65536, at most out_off[i]) bytes that lie directly before out_base + out_off[i].  The caller put them there;
+ *     they are read and never written.
+ *   link[i] == 1 (not for i = 0): block i continues block i-1's chain.  out_off[i] and out_cap[i] are ignored: its output starts where
+ *     block i-1's ended, the whole chain shares the head's out_cap, and its matches reach back up to 65535 bytes into what the chain has
+ *     produced and the head's dictionary.  out_len[i] is the block's own byte count: the block's bytes start at the head's out_off plus
+ *     the out_len of the chain's blocks before it (the library reports no offsets of its own).
+ * status: a match offset of 0 or beyond produced + history is RCX_E_MALFORMED; the block of a chain that does not fit the rest of the
+ * head's out_cap gets RCX_E_OUTPUT_TOO_SMALL; every block after a failed one of its chain gets RCX_E_LZ4_HISTORY and out_len 0; other
+ * chains are not affected.  Nothing outside a head's [out_off, out_off + out_cap) is written.  With link and dict_len NULL the results
+ * (bytes, out_len, in_used, status) are those of rcx_lz4_decode_batch.  A batch costs one launch per block of its longest chain, stream
+ * ordered, no host wait in between; one wave decodes a block (k_lz4_decode_v4's decoder, started behind its history).  Measured on
+ * MI355X, device memory: 4096 independent 64 KiB text blocks 0.943 ms a call (rcx_lz4_decode_batch: 0.501), 256 chains of 16 blocks
+ * 10.1 ms.  From host memory only the dictionaries are copied in and only the bytes the chains wrote are copied back. */
+int rcx_lz4_decode_linked_batch(rcx_ctx*, const rcx_batch*, const uint8_t* link, const uint64_t* dict_len);
 
 /* ---- DEFLATE / zlib / Adler-32 ---------------------------------------------- */
 /* reference: src/flate.rs:195-206,237-246,262-341,343-450 (one RFC-1951 stream
@@ -316,6 +342,9 @@ enum rcx_codec {
     RCX_BWT_SUFFIXES, RCX_BWT_INVERSION_TABLE,
     RCX_DEFLATE_ENCODE, RCX_ZLIB_ENCODE, RCX_GZIP_ENCODE, RCX_CODEC_COUNT
 };
+/* Ids of the batch entry points that rcx_launch_dev, rcx_multi_* and rcx_scratch_bytes do not take (enum rcx_codec stays as it is for
+ * those): they name the entry point to rcx_ctx_set_variant / rcx_ctx_set_param, neither of which has a setting for them yet. */
+enum rcx_xcodec { RCX_XXH32 = 32, RCX_LZ4_DECODE_LINKED = 33, RCX_XCODEC_END = 34 };
 /* scratch bytes (HBM) the codec needs for nblocks blocks of <= max_block bytes.  Required for LZ4 encode, BWT and gzip
  * decode and the DEFLATE / zlib / gzip encoders; for RCX_INFLATE / RCX_ZLIB_DECODE it is what the default (wave-per-stream) decoder needs -- without it
  * rcx_launch_dev falls back to the lane-per-stream kernel (same results, slower on small batches). */

@@ -68,6 +68,7 @@ pub const RCX_E_RLE_LONG_RUN: i32 = 30;
 pub const RCX_E_LZ4_MAGIC: i32 = 40;
 pub const RCX_E_LZ4_VERSION: i32 = 41;
 pub const RCX_E_LZ4_INPUT_TOO_LARGE: i32 = 42;
+pub const RCX_E_LZ4_HISTORY: i32 = 43; // rcx_lz4_decode_linked_batch: an earlier block of the chain failed
 pub const RCX_E_BWT_BLOCK_TOO_LARGE: i32 = 60; // a block of 2^28 bytes or more: this implementation's limit (bwt/mod.rs:451 takes any usize)
 pub const RCX_E_GZIP_MAGIC: i32 = 50;
 pub const RCX_E_GZIP_METHOD: i32 = 51;
@@ -115,6 +116,10 @@ pub const RCX_DEFLATE_ENCODE: c_int = 26;
 pub const RCX_ZLIB_ENCODE: c_int = 27;
 pub const RCX_GZIP_ENCODE: c_int = 28;
 pub const RCX_CODEC_COUNT: c_int = 29;
+// enum rcx_xcodec: batch entry points outside rcx_launch_dev
+pub const RCX_XXH32: c_int = 32;
+pub const RCX_LZ4_DECODE_LINKED: c_int = 33;
+pub const RCX_XCODEC_END: c_int = 34;
 
 #[link(name = "rcx")]
 extern "C" {
@@ -132,6 +137,9 @@ extern "C" {
     // ---- LZ4 high compression (extension: the reference's frame Encoder stores every block, src/lz4.rs:543-545)
     pub fn rcx_lz4_encode_hc_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int) -> c_int;
     pub fn rcx_lz4_hc_scratch_bytes(nblocks: u32, max_block: u64) -> u64;
+    // ---- the LZ4 frame format's device side (extension): XXH32, block decode with history (linked blocks, dictionaries)
+    pub fn rcx_xxh32_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, seed: u32, hash: *mut u32) -> c_int;
+    pub fn rcx_lz4_decode_linked_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, link: *const u8, dict_len: *const u64) -> c_int;
     // ---- DEFLATE / zlib / Adler-32 (src/flate.rs, src/zlib.rs, src/checksum/adler.rs) + the gzip extension
     pub fn rcx_inflate_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32) -> c_int;
     pub fn rcx_zlib_decode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32) -> c_int;

@@ -26,6 +26,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 E_EOF, E_OUTPUT_TOO_SMALL, E_MALFORMED = 1, 2, 3
 E_GZIP_MAGIC, E_GZIP_METHOD, E_GZIP_FLAGS, E_GZIP_CRC, E_GZIP_ISIZE = 50, 51, 52, 53, 54
 E_BWT_BLOCK_TOO_LARGE = 60
+E_LZ4_MAGIC, E_LZ4_VERSION, E_LZ4_INPUT_TOO_LARGE, E_LZ4_HISTORY = 40, 41, 42, 43
 RC_OK, RC_BAD_ARG, RC_NO_DEVICE, RC_HIP_ERROR, RC_NO_MEMORY = 0, -1, -2, -3, -4
 
 EXPORTS = [
@@ -44,6 +45,7 @@ EXPORTS = [
     "rcx_deflate_encode_batch", "rcx_zlib_encode_batch", "rcx_gzip_encode_batch", "rcx_deflate_compression_bound",
     "rcx_lz4_encode_hc_batch", "rcx_lz4_hc_scratch_bytes",
     "rcx_deflate_encode_level_batch", "rcx_zlib_encode_level_batch", "rcx_gzip_encode_level_batch", "rcx_deflate_level_scratch_bytes",
+    "rcx_xxh32_batch", "rcx_lz4_decode_linked_batch",
 ]
 
 
@@ -110,6 +112,8 @@ def lib():
         L.rcx_lz4_hc_scratch_bytes.restype = C.c_uint64
         for name in ("rcx_deflate_encode_level_batch", "rcx_zlib_encode_level_batch", "rcx_gzip_encode_level_batch"):
             getattr(L, name).argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int]
+        L.rcx_xxh32_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_uint32, C.c_void_p]
+        L.rcx_lz4_decode_linked_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p]
         L.rcx_deflate_level_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64]
         L.rcx_deflate_level_scratch_bytes.restype = C.c_uint64
         for name in ("rcx_inflate_batch", "rcx_zlib_decode_batch", "rcx_adler32_batch", "rcx_crc32_batch",

@@ -1,6 +1,6 @@
 """Builds librcx.so (the C-ABI + gfx950 kernels) in-tree with hipcc.  Cross-compiles without a GPU.
 
-The library is six translation units (rcx_api + one per codec family) compiled in parallel and linked once;
+The library is several translation units (rcx_api + one per codec family) compiled in parallel and linked once;
 objects are cached under csrc/build/ and rebuilt when a source they include is newer.
 `ab=True` (or RCX_AB=1 in the environment) builds librcx_ab.so with -DRCX_AB_VARIANTS: the earlier kernel
 generations, profiling instantiations and experiments that benchmarks/ compares against.  The shipped librcx.so
@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-TUS = ["rcx_api", "tu_lz4", "tu_inflate", "tu_bwt", "tu_serial", "tu_deflate_encode", "tu_lz4_hc"]
+TUS = ["rcx_api", "tu_lz4", "tu_inflate", "tu_bwt", "tu_serial", "tu_deflate_encode", "tu_lz4_hc", "tu_lz4_frame"]
 
 
 def _out(ab):

@@ -31,8 +31,12 @@ struct rcx_ctx {
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
     std::string err;
-    int variant[RCX_CODEC_COUNT] = {0};
-    uint32_t param[RCX_CODEC_COUNT] = {0};
+    int variant[RCX_XCODEC_END] = {0};          // (indexed by enum rcx_codec and enum rcx_xcodec)
+    uint32_t param[RCX_XCODEC_END] = {0};
+    // rcx_lz4_decode_linked_batch: the chains of the batch in flight, for launch_codec (device arrays but rounds_off)
+    struct { const uint32_t* order; const uint32_t* head; const uint32_t* dict; uint64_t* eff; const uint32_t* rounds_off; uint32_t nrounds;
+             const uint32_t* h_head; const uint32_t* h_dict; } link = {};        // (h_*: the same tables on the host, for the copies of a host-memory batch)
+    DevBuf d_link;
     DevBuf d_in, d_out, d_desc, d_scratch;
     DevBuf d_apm;                        // apm stretch table + gate bins (filled on first use)
     uint8_t* h_desc = nullptr; size_t h_desc_cap = 0;      // page-locked: the descriptors' way in and the results' way out are small copies the call waits for
@@ -73,7 +77,7 @@ extern "C" void rcx_ctx_destroy(rcx_ctx* c)
 {
     if (!c) return;
     (void)hipStreamSynchronize(c->stream);
-    c->d_in.release(); c->d_out.release(); c->d_desc.release(); c->d_scratch.release(); c->d_apm.release();
+    c->d_in.release(); c->d_out.release(); c->d_desc.release(); c->d_scratch.release(); c->d_apm.release(); c->d_link.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t e : c->piece_ev) (void)hipEventDestroy(e);
@@ -90,16 +94,18 @@ extern "C" int rcx_ctx_set_stream(rcx_ctx* c, void* s)
     return RCX_RC_OK;
 }
 
+static bool codec_id_ok(int codec) { return (codec >= 0 && codec < RCX_CODEC_COUNT) || (codec >= RCX_XXH32 && codec < RCX_XCODEC_END); }
+
 extern "C" int rcx_ctx_set_variant(rcx_ctx* c, int codec, int variant)
 {
-    if (!c || codec < 0 || codec >= RCX_CODEC_COUNT) return RCX_RC_BAD_ARG;
+    if (!c || !codec_id_ok(codec)) return RCX_RC_BAD_ARG;
     c->variant[codec] = variant;
     return RCX_RC_OK;
 }
 
 extern "C" int rcx_ctx_set_param(rcx_ctx* c, int codec, uint32_t value)
 {
-    if (!c || codec < 0 || codec >= RCX_CODEC_COUNT) return RCX_RC_BAD_ARG;
+    if (!c || !codec_id_ok(codec)) return RCX_RC_BAD_ARG;
     c->param[codec] = value;
     if (codec == RCX_LZ4_DECODE || codec == RCX_INFLATE || codec == RCX_ZLIB_DECODE) { c->gate_bad = false; c->gate_bad_calls = 0; }   // (setting a decoder's host-path knobs also ends the back-off a late gate started)
     return RCX_RC_OK;
@@ -131,6 +137,7 @@ extern "C" const char* rcx_status_string(int s)
     case RCX_E_LZ4_MAGIC: return "";
     case RCX_E_LZ4_VERSION: return "";
     case RCX_E_LZ4_INPUT_TOO_LARGE: return "input too large";
+    case RCX_E_LZ4_HISTORY: return "an earlier block of the chain failed";
     case RCX_E_BWT_BLOCK_TOO_LARGE: return "bwt block of 2^28 bytes or more";
     case RCX_E_GZIP_MAGIC: return "not a gzip member";
     case RCX_E_GZIP_METHOD: return "unsupported gzip compression method";
@@ -176,7 +183,7 @@ extern "C" uint64_t rcx_scratch_bytes(int codec, uint32_t nblocks, uint64_t max_
 
 // ---- kernel dispatch (the kernels and their launch code live in the tu_*.hip translation units) ------------------
 // param_over >= 0 replaces the context's codec parameter for this one launch (the *_ctx_batch entry points' `withctx`)
-static int launch_codec(rcx_ctx* c, int codec, rcx_kargs& k, int param_over = -1)
+static int launch_codec(rcx_ctx* c, int codec, rcx_kargs& k, int64_t param_over = -1)
 {
     hipStream_t s = c->stream;
     const uint32_t n = k.nblocks;
@@ -202,6 +209,12 @@ static int launch_codec(rcx_ctx* c, int codec, rcx_kargs& k, int param_over = -1
         break;
     case RCX_CRC32:
         rcx_tu_crc32(s, k);
+        break;
+    case RCX_XXH32:                                              // param_over carries the seed's bits
+        rcx_tu_xxh32(s, k, (uint32_t)param_over);
+        break;
+    case RCX_LZ4_DECODE_LINKED:
+        rcx_tu_lz4_decode_linked(s, k, c->link.order, c->link.rounds_off, c->link.nrounds, c->link.head, c->link.dict, c->link.eff);
         break;
     case RCX_GZIP_DECODE:
         if (k.scratch_bytes < rcx_tu_gzip_scratch(n)) { c->err = "gzip decode: scratch too small"; return RCX_RC_BAD_ARG; }
@@ -280,7 +293,7 @@ extern "C" int rcx_launch_dev(rcx_ctx* c, int codec, const rcx_dev_batch* b, voi
 //   in_off[n] in_len[n] out_off[n] out_cap[n] n_out[n] | out_len[n] in_used[n] | status[n] aux[n]
 static const uint32_t GATE_RETRY = 64;      // calls that go back to one copy in front of the launch after a gate ran into its limit (one descheduling of the calling thread is enough for that)
 static int run_batch(rcx_ctx* c, int codec, const rcx_batch* b, const uint32_t* aux_in, uint32_t* aux_out,
-                     const uint64_t* n_out, bool needs_out, int param_over = -1)
+                     const uint64_t* n_out, bool needs_out, int64_t param_over = -1)
 {
     if (!c) return RCX_RC_BAD_ARG;
     if (!b || (b->nblocks && (!b->in_off || !b->in_len || !b->status))) { c->err = "null descriptor array"; return RCX_RC_BAD_ARG; }
@@ -359,6 +372,14 @@ static int run_batch(rcx_ctx* c, int codec, const rcx_batch* b, const uint32_t* 
         // (and so does the LZ4 HC encoder: a block's slot holds its bound, more than the block takes)
         if ((codec == RCX_DEFLATE_ENCODE || codec == RCX_ZLIB_ENCODE || codec == RCX_GZIP_ENCODE || (codec == RCX_LZ4_ENCODE && param_over > 0)) && out_span)
             HIPCHK(c, hipMemcpyAsync(d_out, b->out_base, out_span, hipMemcpyHostToDevice, s));
+        // the linked LZ4 decoder reads the dictionaries the caller put in front of the chain heads' slots: those ranges alone travel in
+        // (and only what the chains wrote travels back, below)
+        if (codec == RCX_LZ4_DECODE_LINKED)
+            for (uint32_t i = 0; i < n; i++)
+                if (c->link.h_head[i] == i && c->link.h_dict[i]) {
+                    const uint64_t at = b->out_off[i] - c->link.h_dict[i];
+                    HIPCHK(c, hipMemcpyAsync(d_out + at, b->out_base + at, c->link.h_dict[i], hipMemcpyHostToDevice, s));
+                }
     } else if (b->mem != RCX_MEM_DEVICE) { c->err = "bad mem kind"; return RCX_RC_BAD_ARG; }
 
     const size_t N = n;
@@ -572,6 +593,27 @@ static int run_batch(rcx_ctx* c, int codec, const rcx_batch* b, const uint32_t* 
             const uint64_t l = ol[i] < b->out_cap[i] ? ol[i] : b->out_cap[i];
             if (l && b->out_off[i] + l > used_span) used_span = b->out_off[i] + l;
         }
+        if (codec == RCX_LZ4_DECODE_LINKED) {
+            // a chain's bytes lie behind its head's out_off, as many as its blocks' out_len add up to; nothing else of the caller's
+            // buffer changes (the staging buffer never held the caller's bytes between the slots).  Chains that touch travel as one copy.
+            used_span = 0;
+            uint64_t lo = 0, hi = 0;
+            for (uint32_t i = 0; i < n;) {
+                uint64_t sum = 0;
+                uint32_t j = i;
+                do { sum += ol[j]; j++; } while (j < n && c->link.h_head[j] == i);
+                if (sum > b->out_cap[i]) sum = b->out_cap[i];
+                // (a chain whose last block failed may have written part of that block behind the sum: inside its slot, not reported)
+                if (sum && b->out_off[i] == hi) hi += sum;
+                else if (sum) {
+                    if (hi > lo) HIPCHK(c, hipMemcpyAsync(b->out_base + lo, d_out + lo, hi - lo, hipMemcpyDeviceToHost, s));
+                    lo = b->out_off[i]; hi = lo + sum;
+                }
+                i = j;
+            }
+            if (hi > lo) HIPCHK(c, hipMemcpyAsync(b->out_base + lo, d_out + lo, hi - lo, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+        }
         if (used_span) HIPCHK(c, hipMemcpy(b->out_base, d_out, used_span, hipMemcpyDeviceToHost));
     }
     if (b->out_len) memcpy(b->out_len, h64 + 5 * N, N * 8);
@@ -593,6 +635,55 @@ extern "C" int rcx_inflate_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags
 extern "C" int rcx_zlib_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, RCX_ZLIB_DECODE, b, nullptr, flags, nullptr, true); }
 extern "C" int rcx_adler32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* adler) { return run_batch(c, RCX_ADLER32, b, nullptr, adler, nullptr, false); }
 extern "C" int rcx_crc32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* crc) { return run_batch(c, RCX_CRC32, b, nullptr, crc, nullptr, false); }
+extern "C" int rcx_xxh32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t seed, uint32_t* hash)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    if (b && b->nblocks && !hash) { c->err = "xxh32: null hash array"; return RCX_RC_BAD_ARG; }
+    return run_batch(c, RCX_XXH32, b, nullptr, hash, nullptr, false, (int64_t)seed);
+}
+// The chains are laid out on the host -- every block's head, its depth, the blocks sorted by depth -- and the batch goes through
+// run_batch like any other: launch_codec issues one launch per depth (k_lz4_linked.hip).  A linked block's out_off / out_cap are the
+// caller's to leave unset: the batch run_batch sees has 0 / 0 there.
+extern "C" int rcx_lz4_decode_linked_batch(rcx_ctx* c, const rcx_batch* b, const uint8_t* link, const uint64_t* dict_len)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    if (!b || (b->nblocks && (!b->out_off || !b->out_cap))) { c->err = "null descriptor array"; return RCX_RC_BAD_ARG; }
+    const uint32_t n = b->nblocks;
+    if (n == 0) return RCX_RC_OK;
+    if (link && link[0]) { c->err = "lz4 linked decode: block 0 cannot continue a chain"; return RCX_RC_BAD_ARG; }
+    std::vector<uint64_t> ooff(n), ocap(n);
+    std::vector<uint32_t> tab(3 * (size_t)n), depth(n), rounds(2, 0);
+    uint32_t* order = tab.data(); uint32_t* head = order + n; uint32_t* dict = head + n;
+    uint32_t nrounds = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const bool cont = link && link[i];
+        head[i] = cont ? head[i - 1] : i;
+        depth[i] = cont ? depth[i - 1] + 1 : 0;
+        if (depth[i] + 1 > nrounds) nrounds = depth[i] + 1;
+        ooff[i] = cont ? 0 : b->out_off[i];
+        ocap[i] = cont ? 0 : b->out_cap[i];
+        uint64_t d = (!cont && dict_len) ? dict_len[i] : 0;
+        if (d > ooff[i]) { c->err = "block " + std::to_string(i) + ": dict_len reaches below out_base"; return RCX_RC_BAD_ARG; }
+        dict[i] = (uint32_t)(d > 65536u ? 65536u : d);
+    }
+    rounds.assign(nrounds + 2, 0);                              // counting sort by depth
+    for (uint32_t i = 0; i < n; i++) rounds[depth[i] + 2]++;
+    for (uint32_t r = 2; r < nrounds + 2; r++) rounds[r] += rounds[r - 1];
+    for (uint32_t i = 0; i < n; i++) order[rounds[depth[i] + 1]++] = i;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t tab_bytes = ((3 * (size_t)n * 4 + 7) & ~(size_t)7);
+    HIPCHK(c, c->d_link.reserve(tab_bytes + (size_t)n * 8));
+    HIPCHK(c, hipMemcpyAsync(c->d_link.p, tab.data(), 3 * (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    c->link.order = (const uint32_t*)c->d_link.p; c->link.head = c->link.order + n; c->link.dict = c->link.head + n;
+    c->link.eff = (uint64_t*)((uint8_t*)c->d_link.p + tab_bytes);
+    c->link.rounds_off = rounds.data(); c->link.nrounds = nrounds;
+    c->link.h_head = head; c->link.h_dict = dict;
+    rcx_batch bb = *b;
+    bb.out_off = ooff.data(); bb.out_cap = ocap.data();
+    const int rc = run_batch(c, RCX_LZ4_DECODE_LINKED, &bb, nullptr, nullptr, nullptr, true);      // (waits for the stream: the tables above may go)
+    c->link = {};
+    return rc;
+}
 extern "C" int rcx_gzip_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, RCX_GZIP_DECODE, b, nullptr, flags, nullptr, true); }
 extern "C" int rcx_deflate_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_DEFLATE_ENCODE, b, nullptr, nullptr, nullptr, true, 1); }
 extern "C" int rcx_zlib_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_ZLIB_ENCODE, b, nullptr, nullptr, nullptr, true, 1); }

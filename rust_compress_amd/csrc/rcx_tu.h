@@ -42,3 +42,9 @@ uint64_t rcx_tu_deflate_level_scratch(uint32_t nblocks, uint64_t nsegs);
 int rcx_tu_lz4_hc(hipStream_t s, rcx_kargs& k, int level, std::string& err);
 uint64_t rcx_tu_lz4_hc_scratch(uint32_t nblocks, uint64_t nsegs);
 uint64_t rcx_tu_lz4_hc_segments(uint64_t len);
+// tu_lz4_frame.hip: XXH32 of every block; LZ4 block decode with history (linked blocks, dictionaries), one launch per chain depth
+void rcx_tu_xxh32(hipStream_t s, rcx_kargs& k, uint32_t seed);
+// order[rounds_off[r] .. rounds_off[r + 1]): the blocks at depth r of their chains (rounds_off is a HOST array); head[i]: block i's chain
+// head; dict[i]: a head's dictionary bytes; eff[i] (written): where block i's output starts in out_base.  Device arrays.
+void rcx_tu_lz4_decode_linked(hipStream_t s, rcx_kargs& k, const uint32_t* order, const uint32_t* rounds_off, uint32_t nrounds,
+                              const uint32_t* head, const uint32_t* dict, uint64_t* eff);
