@@ -357,11 +357,15 @@ int rcx_launch_dev(rcx_ctx*, int codec, const rcx_dev_batch*, void* scratch, uin
 int rcx_hbm_copy_probe(rcx_ctx*, uint64_t bytes, int reps, double* gb_per_s);
 /* kernel variant knob for A/B measurements (0 = default/best). */
 int rcx_ctx_set_variant(rcx_ctx*, int codec, int variant);
-/* codec parameter for rcx_launch_dev (the *_batch entry points take it as an argument): the rate of RCX_ARI_BINARY_*;
- * RCX_LZ4_DECODE: bit 0 = host-memory batches by plain copies (see rcx_lz4_decode_batch), bits 8-15 / 16-23 tuning of the ranges;
- * RCX_LZ4_ENCODE: 0 = the reference's encoder, 1..12 = the HC level (see rcx_lz4_encode_hc_batch); the batch calls ignore it;
+/* codec parameter for rcx_launch_dev (the *_batch entry points take it as an argument and neither read nor write it): the rate of
+ * RCX_ARI_BINARY_* (also what rcx_multi_batch, which has no argument for it, codes with);
+ * RCX_LZ4_DECODE, RCX_INFLATE, RCX_ZLIB_DECODE, RCX_GZIP_DECODE: bit 0 = host-memory batches by plain copies (see rcx_lz4_decode_batch),
+ * bits 8-15 / 16-23 tuning of the ranges -- the one parameter the batch calls do read;
+ * RCX_LZ4_ENCODE: 0 = the reference's encoder, 1..12 = the HC level (see rcx_lz4_encode_hc_batch); the batch calls ignore it,
+ * rcx_multi_batch included (it runs rcx_lz4_encode_batch's encoder);
  * RCX_DEFLATE_ENCODE / RCX_ZLIB_ENCODE / RCX_GZIP_ENCODE: 0 or 1..9 = the level (see rcx_deflate_encode_level_batch); the batch calls
- * ignore it */
+ * ignore it, rcx_multi_batch included (level 1);
+ * RCX_DC_ENCODE / RCX_DC_DECODE: 1 = with the coding contexts (rcx_dc_encode_ctx_batch); the batch calls ignore it */
 int rcx_ctx_set_param(rcx_ctx*, int codec, uint32_t value);
 
 /* ---- more than one device ---------------------------------

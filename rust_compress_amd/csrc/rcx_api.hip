@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rcx_tu.h"
+#include "rcx_plan.h"
 
 struct DevBuf {
     void* p = nullptr; size_t cap = 0;
@@ -33,10 +34,7 @@ struct rcx_ctx {
     std::string err;
     int variant[RCX_XCODEC_END] = {0};          // (indexed by enum rcx_codec and enum rcx_xcodec)
     uint32_t param[RCX_XCODEC_END] = {0};
-    // rcx_lz4_decode_linked_batch: the chains of the batch in flight, for launch_codec (device arrays but rounds_off)
-    struct { const uint32_t* order; const uint32_t* head; const uint32_t* dict; uint64_t* eff; const uint32_t* rounds_off; uint32_t nrounds;
-             const uint32_t* h_head; const uint32_t* h_dict; } link = {};        // (h_*: the same tables on the host, for the copies of a host-memory batch)
-    DevBuf d_link;
+    DevBuf d_link;                       // rcx_lz4_decode_linked_batch: the chains' tables (order | head | dict | eff)
     DevBuf d_in, d_out, d_desc, d_scratch;
     DevBuf d_apm;                        // apm stretch table + gate bins (filled on first use)
     uint8_t* h_desc = nullptr; size_t h_desc_cap = 0;      // page-locked: the descriptors' way in and the results' way out are small copies the call waits for
@@ -181,11 +179,108 @@ extern "C" uint64_t rcx_scratch_bytes(int codec, uint32_t nblocks, uint64_t max_
     }
 }
 
+// ---- one call's record -------------------------------------------------------------------------------------------------------------
+// rcx_lz4_decode_linked_batch: the chains of the batch (rcx_plan.h) and their tables in d_link
+struct link_tables { const rcx_chain_plan* plan; const uint32_t* order; const uint32_t* head; const uint32_t* dict; uint64_t* eff; };
+// What an entry point asks of run_batch and launch_codec.  Nothing of a call travels through the context: the context keeps the kernel
+// variants and the decoders' host-path knobs (bit 0: plain copies, bits 8-23: range tuning), and rcx_launch_dev alone reads its parameter.
+struct rcx_call {
+    int codec;
+    uint32_t param;                      // the EFFECTIVE parameter, resolved once by the entry point: LZ4 HC / DEFLATE level, DC withctx, ARI binary rate
+    const uint32_t* aux_in; uint32_t* aux_out; const uint64_t* n_out;
+    bool needs_out;
+    uint32_t seed;                       // XXH32
+    const link_tables* link;             // linked LZ4 decode, else null
+};
+
+// ---- per-codec traits of the host path ------------------------------------------------------------------------------------------------
+enum mirror_kind { MIRROR_NONE, MIRROR_LZ4, MIRROR_INFLATE };          // may the launch store into a page-locked output buffer itself?
+enum scratch_rule { SCRATCH_BY_CODEC,                                  // rcx_scratch_bytes
+                    SCRATCH_DEFLATE_SEGS, SCRATCH_DEFLATE_LEVEL_SEGS,  // the staging of the real segments (+ chains, parse: levels 2..9)
+                    SCRATCH_HC_SEGS,                                   // HC: the chains and parse of the real segments
+                    SCRATCH_DC_OPTIONAL };                             // chunk states: none with contexts, and none when they cannot be had
+enum back_policy { BACK_USED_SPAN, BACK_INFLATE /* mirrored: the streams the first pass handed back */, BACK_CHAINS };
+struct codec_traits {
+    bool needs_out;
+    mirror_kind mirror;
+    bool ranges;                         // may its input arrive in ranges under the launch?
+    bool preload_out;                    // the staged output span starts as the caller's bytes
+    scratch_rule scratch;
+    back_policy back;
+};
+static codec_traits traits_of(int codec, uint32_t param)
+{
+    codec_traits t = {true, MIRROR_NONE, false, false, SCRATCH_BY_CODEC, BACK_USED_SPAN};
+    switch (codec) {
+    case RCX_LZ4_DECODE: t.mirror = MIRROR_LZ4; t.ranges = true; break;
+    // (the inflate front end drains through the same window; the streams its first pass hands back are copied out behind the second)
+    case RCX_INFLATE: case RCX_ZLIB_DECODE: t.mirror = MIRROR_INFLATE; t.ranges = true; t.back = BACK_INFLATE; break;
+    // (gzip members: their headers are parsed by a kernel of its own in front of the decoder, which wants every member there)
+    case RCX_GZIP_DECODE: t.mirror = MIRROR_INFLATE; t.back = BACK_INFLATE; break;
+    // the DEFLATE encoders promise that no byte of the caller's buffer outside the streams they write changes: the copy back takes the
+    // whole span, so the span starts as the caller's bytes
+    case RCX_DEFLATE_ENCODE: case RCX_ZLIB_ENCODE: case RCX_GZIP_ENCODE:
+        t.preload_out = true; t.scratch = param > 1 ? SCRATCH_DEFLATE_LEVEL_SEGS : SCRATCH_DEFLATE_SEGS; break;
+    // (and so does the LZ4 HC encoder: a block's slot holds its bound, more than the block takes)
+    case RCX_LZ4_ENCODE: if (param) { t.preload_out = true; t.scratch = SCRATCH_HC_SEGS; } break;
+    case RCX_DC_ENCODE: t.scratch = SCRATCH_DC_OPTIONAL; break;
+    case RCX_LZ4_DECODE_LINKED: t.back = BACK_CHAINS; break;
+    case RCX_ADLER32: case RCX_CRC32: case RCX_XXH32: t.needs_out = false; break;
+    default: break;
+    }
+    return t;
+}
+static rcx_call call_of(int codec, uint32_t param = 0, const uint32_t* aux_in = nullptr, uint32_t* aux_out = nullptr, const uint64_t* n_out = nullptr)
+{
+    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr};
+}
+
+// ---- kernel arguments: built here and nowhere else ---------------------------------------------------------------------------------------
+struct gate_args { uint32_t* gate; const uint32_t* gate_host; uint32_t seq, ticks; const rcx_range_plan* ranges; };
+static rcx_kargs make_kargs(const rcx_dev_batch& b, const uint64_t* n_out, void* scratch, uint64_t scratch_bytes,
+                            uint8_t* out_mirror = nullptr, const gate_args* g = nullptr)
+{
+    rcx_kargs k = {};
+    k.in_base = b.in_base; k.in_off = b.in_off; k.in_len = b.in_len;
+    k.out_base = b.out_base; k.out_off = b.out_off; k.out_cap = b.out_cap;
+    k.out_len = b.out_len; k.in_used = b.in_used; k.status = b.status; k.aux = b.aux;
+    k.n_out = n_out; k.scratch = scratch; k.scratch_bytes = scratch_bytes; k.nblocks = b.nblocks; k.out_mirror = out_mirror;
+    for (int i = 0; i < 15; i++) k.gate_bnd[i] = 0xffffffffu;
+    if (g) {
+        k.gate = g->gate; k.gate_host = g->gate_host; k.gate_seq = g->seq; k.gate_ticks = g->ticks;
+        // (range 0 waits at a gate like the others: the launch is on its way to the device while the first bytes are)
+        k.gate_all = 1;
+        for (uint32_t pc = 1; pc < g->ranges->pieces(); pc++) k.gate_bnd[pc - 1] = g->ranges->bnd[pc];
+    }
+    return k;
+}
+
+// the stretch table and gate bins of the APM coder (apm.rs:53-59, 69-75, 144-154 through this host's libm), filled on first use
+static int apm_tables(rcx_ctx* c)
+{
+    if (c->d_apm.p) return RCX_RC_OK;
+    std::vector<uint16_t> h(4096 + 32, 0);
+    for (uint32_t fp = 0; fp < 4096; fp++) {
+        const float p = (float)fp / 4096.0f;
+        const float w = logf(p / (1.0f - p)) * 2048.0f;
+        h[fp] = (w > -32769.0f && w < 32768.0f) ? (uint16_t)(int16_t)w : (uint16_t)0x8000;
+    }
+    for (int i = 0; i < 17; i++) {
+        const float rp = (float)i / 8.0f - 1.0f;
+        const int16_t wp = (int16_t)(rp * 2048.0f);
+        const float pr = 1.0f / (1.0f + expf(-((float)wp / 2048.0f)));
+        h[4096 + i] = (uint16_t)(pr * 4096.0f);
+    }
+    HIPCHK(c, c->d_apm.reserve(h.size() * 2));
+    HIPCHK(c, hipMemcpy(c->d_apm.p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+    return RCX_RC_OK;
+}
+
 // ---- kernel dispatch (the kernels and their launch code live in the tu_*.hip translation units) ------------------
-// param_over >= 0 replaces the context's codec parameter for this one launch (the *_ctx_batch entry points' `withctx`)
-static int launch_codec(rcx_ctx* c, int codec, rcx_kargs& k, int64_t param_over = -1)
+static int launch_codec(rcx_ctx* c, const rcx_call& call, rcx_kargs& k)
 {
     hipStream_t s = c->stream;
+    const int codec = call.codec;
     const uint32_t n = k.nblocks;
     if (n == 0) return RCX_RC_OK;
     const int v = c->variant[codec];
@@ -195,7 +290,7 @@ static int launch_codec(rcx_ctx* c, int codec, rcx_kargs& k, int64_t param_over 
         if (rc) return rc;
         break; }
     case RCX_LZ4_ENCODE: {                                       // the codec parameter: 0 the reference's greedy encoder, 1..12 the HC level
-        const uint32_t level = param_over >= 0 ? (uint32_t)param_over : c->param[codec];
+        const uint32_t level = call.param;
         if (level > 12) { c->err = "lz4 encode: level must be 0 (reference encoder) or 1..12 (HC)"; return RCX_RC_BAD_ARG; }
         int rc = level ? rcx_tu_lz4_hc(s, k, (int)level, c->err) : rcx_tu_lz4_encode(s, k, v, c->err);
         if (rc) return rc;
@@ -210,18 +305,20 @@ static int launch_codec(rcx_ctx* c, int codec, rcx_kargs& k, int64_t param_over 
     case RCX_CRC32:
         rcx_tu_crc32(s, k);
         break;
-    case RCX_XXH32:                                              // param_over carries the seed's bits
-        rcx_tu_xxh32(s, k, (uint32_t)param_over);
+    case RCX_XXH32:
+        rcx_tu_xxh32(s, k, call.seed);
         break;
     case RCX_LZ4_DECODE_LINKED:
-        rcx_tu_lz4_decode_linked(s, k, c->link.order, c->link.rounds_off, c->link.nrounds, c->link.head, c->link.dict, c->link.eff);
+        if (!call.link) { c->err = "lz4 linked decode: use rcx_lz4_decode_linked_batch"; return RCX_RC_BAD_ARG; }
+        rcx_tu_lz4_decode_linked(s, k, call.link->order, call.link->plan->rounds_off.data(), call.link->plan->nrounds, call.link->head,
+                                 call.link->dict, call.link->eff);
         break;
     case RCX_GZIP_DECODE:
         if (k.scratch_bytes < rcx_tu_gzip_scratch(n)) { c->err = "gzip decode: scratch too small"; return RCX_RC_BAD_ARG; }
         rcx_tu_gzip_decode(s, k, v);
         break;
     case RCX_DEFLATE_ENCODE: case RCX_ZLIB_ENCODE: case RCX_GZIP_ENCODE: {   // the codec parameter: the level, 0 (as 1) or 1..9
-        const uint32_t level = param_over >= 0 ? (uint32_t)param_over : c->param[codec];
+        const uint32_t level = call.param;
         if (level > 9) { c->err = "deflate encode: level must be 0 or 1..9"; return RCX_RC_BAD_ARG; }
         const int fmt = codec == RCX_DEFLATE_ENCODE ? 0 : codec == RCX_ZLIB_ENCODE ? 1 : 2;
         int rc = level > 1 ? rcx_tu_deflate_encode_level(s, k, fmt, (int)level, c->err) : rcx_tu_deflate_encode(s, k, fmt, c->err);
@@ -240,32 +337,18 @@ static int launch_codec(rcx_ctx* c, int codec, rcx_kargs& k, int64_t param_over 
         if (rc) return rc;
         break; }
     case RCX_ARI_APM_ENCODE: case RCX_ARI_APM_DECODE: {
-        if (!c->d_apm.p) {                                       // apm.rs:53-59, 69-75, 144-154 through this host's libm
-            std::vector<uint16_t> h(4096 + 32, 0);
-            for (uint32_t fp = 0; fp < 4096; fp++) {
-                const float p = (float)fp / 4096.0f;
-                const float w = logf(p / (1.0f - p)) * 2048.0f;
-                h[fp] = (w > -32769.0f && w < 32768.0f) ? (uint16_t)(int16_t)w : (uint16_t)0x8000;
-            }
-            for (int i = 0; i < 17; i++) {
-                const float rp = (float)i / 8.0f - 1.0f;
-                const int16_t wp = (int16_t)(rp * 2048.0f);
-                const float pr = 1.0f / (1.0f + expf(-((float)wp / 2048.0f)));
-                h[4096 + i] = (uint16_t)(pr * 4096.0f);
-            }
-            HIPCHK(c, c->d_apm.reserve(h.size() * 2));
-            HIPCHK(c, hipMemcpy(c->d_apm.p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-        }
+        const int rca = apm_tables(c);
+        if (rca) return rca;
         k.scratch = c->d_apm.p; k.scratch_bytes = (4096 + 32) * 2;
         rcx_tu_serial(s, codec, k, v, 0);
         break; }
     case RCX_ARI_BINARY_ENCODE: case RCX_ARI_BINARY_DECODE:
-        if (c->param[codec] < 1 || c->param[codec] > 31) { c->err = "ari binary: rate must be 1..31"; return RCX_RC_BAD_ARG; }
+        if (call.param < 1 || call.param > 31) { c->err = "ari binary: rate must be 1..31"; return RCX_RC_BAD_ARG; }
         [[fallthrough]];
     case RCX_MTF_ENCODE: case RCX_MTF_DECODE: case RCX_DC_ENCODE: case RCX_DC_DECODE:
     case RCX_ARI_PROXY_ENCODE: case RCX_ARI_PROXY_DECODE:
     case RCX_ARI_BYTE_ENCODE: case RCX_ARI_BYTE_DECODE: case RCX_RLE_ENCODE: case RCX_RLE_DECODE:
-        rcx_tu_serial(s, codec, k, v, param_over >= 0 ? (uint32_t)param_over : c->param[codec]);
+        rcx_tu_serial(s, codec, k, v, call.param);
         break;
     default:
         c->err = "unknown codec";
@@ -279,113 +362,118 @@ extern "C" int rcx_launch_dev(rcx_ctx* c, int codec, const rcx_dev_batch* b, voi
 {
     if (!c || !b || codec < 0 || codec >= RCX_CODEC_COUNT) return RCX_RC_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    rcx_kargs k;
-    k.in_base = b->in_base; k.in_off = b->in_off; k.in_len = b->in_len;
-    k.out_base = b->out_base; k.out_off = b->out_off; k.out_cap = b->out_cap;
-    k.out_len = b->out_len; k.in_used = b->in_used; k.status = b->status; k.aux = b->aux;
-    k.n_out = nullptr; k.scratch = scratch; k.scratch_bytes = scratch_bytes; k.nblocks = b->nblocks; k.out_mirror = nullptr; k.gate = nullptr; k.gate_all = 0;
     if (codec == RCX_DC_DECODE) { c->err = "dc decode needs n_out: use rcx_dc_decode_batch"; return RCX_RC_BAD_ARG; }
-    return launch_codec(c, codec, k);
+    rcx_kargs k = make_kargs(*b, nullptr, scratch, scratch_bytes);
+    return launch_codec(c, call_of(codec, c->param[codec]), k);          // (the one place a codec's parameter comes from the context: include/rcx.h)
 }
 
 // ---- host-descriptor batch path -------------------------------------------------------------------
+// run_batch is a sequence of stages over one batch_state; every stage enqueues on the context's stream in the order it is called.
 // Descriptor block layout in HBM (all 8-byte aligned):
 //   in_off[n] in_len[n] out_off[n] out_cap[n] n_out[n] | out_len[n] in_used[n] | status[n] aux[n]
 static const uint32_t GATE_RETRY = 64;      // calls that go back to one copy in front of the launch after a gate ran into its limit (one descheduling of the calling thread is enough for that)
-static int run_batch(rcx_ctx* c, int codec, const rcx_batch* b, const uint32_t* aux_in, uint32_t* aux_out,
-                     const uint64_t* n_out, bool needs_out, int64_t param_over = -1)
-{
-    if (!c) return RCX_RC_BAD_ARG;
-    if (!b || (b->nblocks && (!b->in_off || !b->in_len || !b->status))) { c->err = "null descriptor array"; return RCX_RC_BAD_ARG; }
-    if (needs_out && b->nblocks && (!b->out_off || !b->out_cap || !b->out_len)) { c->err = "null output descriptor"; return RCX_RC_BAD_ARG; }
-    const uint32_t n = b->nblocks;
-    if (n == 0) return RCX_RC_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    uint64_t in_span = 0, out_span = 0, max_block = 0, max_in = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        // the kernels index a block with 32-bit offsets: a block of 4 GiB or more (or a range that wraps) is a caller error,
-        // not something to decode a prefix of
-        if (b->in_len[i] >> 32 || b->in_off[i] + b->in_len[i] < b->in_off[i] ||
-            (needs_out && (b->out_cap[i] >> 32 || b->out_off[i] + b->out_cap[i] < b->out_off[i]))) {
-            c->err = "block " + std::to_string(i) + ": lengths of 4 GiB or more are not supported (per-block limit 2^32 - 1 bytes)";
-            return RCX_RC_BAD_ARG;
-        }
-        const uint64_t e = b->in_off[i] + b->in_len[i];
-        if (e > in_span) in_span = e;
-        if (b->in_len[i] > max_block) max_block = b->in_len[i];
-        if (b->in_len[i] > max_in) max_in = b->in_len[i];
-        if (needs_out) {
-            const uint64_t o = b->out_off[i] + b->out_cap[i];
-            if (o > out_span) out_span = o;
-            if (b->out_cap[i] > max_block) max_block = b->out_cap[i];
-        }
-    }
-    if ((in_span && !b->in_base) || (out_span && !b->out_base)) { c->err = "null data pointer"; return RCX_RC_BAD_ARG; }
-    const uint8_t* d_in = b->in_base;
-    uint8_t* d_out = b->out_base;
-    // LZ4 decode from host memory into a PAGE-LOCKED output buffer (hipHostMalloc / hipHostRegister: the device can address it):
-    // the decoder stores every byte that leaves its window a second time straight into that buffer (k_lz4_decode_v4.hip, MIRROR),
-    // so the decoded bytes cross PCIe while the launch runs and no device-to-host copy follows it; and the compressed bytes travel in
-    // as block ranges on a copy stream while the launch already decodes the ranges before them (below).  One copy
-    // each way (what every other codec and a pageable buffer get) costs in + kernel + out = 1.8 + 0.5 + 4.9 ms on the headline
-    // workload; this is the outbound 4.9 ms and little else.  rcx_ctx_set_param(ctx, RCX_LZ4_DECODE, 1) keeps the plain copies.
-    uint8_t* mirror = nullptr;
-    uint32_t pieces = 1;
-    const bool inf_mirror = (codec == RCX_INFLATE || codec == RCX_ZLIB_DECODE || codec == RCX_GZIP_DECODE) && !(c->param[codec] & 1u);    // (the inflate front end drains through the same window; the
-                                                                                                              //  streams its first pass hands back are copied out behind the second)
-    if (b->mem == RCX_MEM_HOST && (codec == RCX_LZ4_DECODE || (inf_mirror && rcx_tu_inflate_mirrors(n, 0))) && out_span && c->variant[codec] == 0 && !(c->param[codec] & 1u)) {
-        hipPointerAttribute_t at;
-        // (the WHOLE span must be page-locked and mapped as one range: a buffer registered only in part would take the kernel's stores
-        //  into unmapped addresses -- the last byte's attributes must continue the first's)
-        auto covered = [](const void* base, uint64_t span, hipPointerAttribute_t& first) {
-            hipPointerAttribute_t last;
-            if (hipPointerGetAttributes(&first, base) != hipSuccess || first.type != hipMemoryTypeHost || !first.devicePointer) return false;
-            if (span <= 1) return true;
-            if (hipPointerGetAttributes(&last, (const uint8_t*)base + span - 1) != hipSuccess || last.type != hipMemoryTypeHost || !last.devicePointer) return false;
-            return (const uint8_t*)last.devicePointer == (const uint8_t*)first.devicePointer + (span - 1);
-        };
-        if (c->gate_bad && c->gate_bad_calls && --c->gate_bad_calls == 0) c->gate_bad = false;
-        if (covered(b->out_base, out_span, at)) {
-            mirror = (uint8_t*)at.devicePointer;
-            // (ranges only from page-locked INPUT: a pageable buffer is staged piece by piece, by copies that may need the compute
-            // units the waiting blocks would hold)
-            hipPointerAttribute_t ai;
-            // (gzip members: their headers are parsed by a kernel of its own in front of the decoder, which wants every member there)
-            if (codec != RCX_GZIP_DECODE && in_span && !c->gate_bad && covered(b->in_base, in_span, ai)) {
-                pieces = ((c->param[codec] >> 8) & 255u) ? ((c->param[codec] >> 8) & 255u) : 16u;
-                if (pieces > 16u) pieces = 16u;             // (the most; see below)
-                if (pieces > n / 128u) pieces = n / 128u ? n / 128u : 1u;
-            } else (void)hipGetLastError();
-        } else (void)hipGetLastError();
-    }
-    size_t out_shift = 0;
-    if (b->mem == RCX_MEM_HOST) {
-        out_shift = mirror ? (size_t)((uintptr_t)mirror & 255u) : 0;           // the copy in HBM and the host buffer: the same alignment
-        HIPCHK(c, c->d_in.reserve(in_span + 64));
-        HIPCHK(c, c->d_out.reserve(out_span + out_shift + 64));
-        if (in_span && pieces <= 1) HIPCHK(c, hipMemcpyAsync(c->d_in.p, b->in_base, in_span, hipMemcpyHostToDevice, s));
-        d_in = (const uint8_t*)c->d_in.p;
-        d_out = (uint8_t*)c->d_out.p + out_shift;
-        // the DEFLATE encoders promise that no byte of the caller's buffer outside the streams they write changes: the copy back below
-        // takes the whole span, so the span starts as the caller's bytes
-        // (and so does the LZ4 HC encoder: a block's slot holds its bound, more than the block takes)
-        if ((codec == RCX_DEFLATE_ENCODE || codec == RCX_ZLIB_ENCODE || codec == RCX_GZIP_ENCODE || (codec == RCX_LZ4_ENCODE && param_over > 0)) && out_span)
-            HIPCHK(c, hipMemcpyAsync(d_out, b->out_base, out_span, hipMemcpyHostToDevice, s));
-        // the linked LZ4 decoder reads the dictionaries the caller put in front of the chain heads' slots: those ranges alone travel in
-        // (and only what the chains wrote travels back, below)
-        if (codec == RCX_LZ4_DECODE_LINKED)
-            for (uint32_t i = 0; i < n; i++)
-                if (c->link.h_head[i] == i && c->link.h_dict[i]) {
-                    const uint64_t at = b->out_off[i] - c->link.h_dict[i];
-                    HIPCHK(c, hipMemcpyAsync(d_out + at, b->out_base + at, c->link.h_dict[i], hipMemcpyHostToDevice, s));
-                }
-    } else if (b->mem != RCX_MEM_DEVICE) { c->err = "bad mem kind"; return RCX_RC_BAD_ARG; }
+struct batch_state {
+    const rcx_batch* b = nullptr;
+    uint32_t n = 0;
+    codec_traits t = {};
+    rcx_spans sp;
+    const uint8_t* d_in = nullptr; uint8_t* d_out = nullptr;        // the batch's bytes as the kernels see them
+    uint8_t* mirror = nullptr;                                       // the caller's page-locked output buffer as the device sees it, or null
+    uint32_t pieces = 1;                                             // input ranges (1: one copy in front of the launch)
+    rcx_range_plan ranges;
+    uint64_t* h64 = nullptr; int32_t* h_status = nullptr; uint32_t* h_aux = nullptr;     // the descriptor block, page-locked
+    rcx_dev_batch dv = {};                                           // ... and in HBM
+    const uint64_t* d_n_out = nullptr;
+    void* scratch = nullptr; uint64_t scratch_bytes = 0;
+    rcx_kargs k = {};
+    bool gated = false;
+    const uint64_t* out_len() const { return h64 + 5 * (size_t)n; }
+};
+#define STAGE(x) do { const int rc_ = (x); if (rc_ != RCX_RC_OK) return rc_; } while (0)
 
-    const size_t N = n;
-    const size_t in_words = 5 * N;                 // u64
-    const size_t res_words = 2 * N;                // u64
-    const size_t desc_bytes = (in_words + res_words) * 8 + 2 * N * 4 + 64;
+// stage 1: the arguments, the spans and the per-block limits
+static int check_batch(rcx_ctx* c, const rcx_call& call, const rcx_batch* b, batch_state& st)
+{
+    if (!b || (b->nblocks && (!b->in_off || !b->in_len || !b->status))) { c->err = "null descriptor array"; return RCX_RC_BAD_ARG; }
+    if (call.needs_out && b->nblocks && (!b->out_off || !b->out_cap || !b->out_len)) { c->err = "null output descriptor"; return RCX_RC_BAD_ARG; }
+    st.b = b; st.n = b->nblocks; st.t = traits_of(call.codec, call.param);
+    if (st.n == 0) return RCX_RC_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!rcx_plan_spans(st.n, b->in_off, b->in_len, call.needs_out ? b->out_off : nullptr, call.needs_out ? b->out_cap : nullptr, st.sp, c->err))
+        return RCX_RC_BAD_ARG;
+    if ((st.sp.in_span && !b->in_base) || (st.sp.out_span && !b->out_base)) { c->err = "null data pointer"; return RCX_RC_BAD_ARG; }
+    if (b->mem != RCX_MEM_HOST && b->mem != RCX_MEM_DEVICE) { c->err = "bad mem kind"; return RCX_RC_BAD_ARG; }
+    return RCX_RC_OK;
+}
+
+// (the WHOLE span must be page-locked and mapped as one range: a buffer registered only in part would take the kernel's stores
+//  into unmapped addresses -- the last byte's attributes must continue the first's)
+static bool page_locked(const void* base, uint64_t span, hipPointerAttribute_t& first)
+{
+    hipPointerAttribute_t last;
+    if (hipPointerGetAttributes(&first, base) != hipSuccess || first.type != hipMemoryTypeHost || !first.devicePointer) return false;
+    if (span <= 1) return true;
+    if (hipPointerGetAttributes(&last, (const uint8_t*)base + span - 1) != hipSuccess || last.type != hipMemoryTypeHost || !last.devicePointer) return false;
+    return (const uint8_t*)last.devicePointer == (const uint8_t*)first.devicePointer + (span - 1);
+}
+
+// stage 2: mirror and ranges.
+// LZ4 decode from host memory into a PAGE-LOCKED output buffer (hipHostMalloc / hipHostRegister: the device can address it):
+// the decoder stores every byte that leaves its window a second time straight into that buffer (k_lz4_decode_v4.hip, MIRROR),
+// so the decoded bytes cross PCIe while the launch runs and no device-to-host copy follows it; and the compressed bytes travel in
+// as block ranges on a copy stream while the launch already decodes the ranges before them (launch_gated).  One copy
+// each way (what every other codec and a pageable buffer get) costs in + kernel + out = 1.8 + 0.5 + 4.9 ms on the headline
+// workload; this is the outbound 4.9 ms and little else.  rcx_ctx_set_param(ctx, RCX_LZ4_DECODE, 1) keeps the plain copies.
+static void decide_mirror(rcx_ctx* c, const rcx_call& call, batch_state& st)
+{
+    const rcx_batch* b = st.b;
+    const uint32_t knobs = c->param[call.codec];
+    st.mirror = nullptr; st.pieces = 1; st.gated = false;
+    if (b->mem != RCX_MEM_HOST || st.t.mirror == MIRROR_NONE || (knobs & 1u) || c->variant[call.codec] != 0 || !st.sp.out_span) return;
+    if (st.t.mirror == MIRROR_INFLATE && !rcx_tu_inflate_mirrors(st.n, 0)) return;
+    if (c->gate_bad && c->gate_bad_calls && --c->gate_bad_calls == 0) c->gate_bad = false;
+    hipPointerAttribute_t at, ai;
+    if (!page_locked(b->out_base, st.sp.out_span, at)) { (void)hipGetLastError(); return; }
+    st.mirror = (uint8_t*)at.devicePointer;
+    // (ranges only from page-locked INPUT: a pageable buffer is staged piece by piece, by copies that may need the compute
+    // units the waiting blocks would hold)
+    if (st.t.ranges && st.sp.in_span && !c->gate_bad && page_locked(b->in_base, st.sp.in_span, ai)) st.pieces = rcx_plan_piece_count(st.n, (knobs >> 8) & 255u);
+    else (void)hipGetLastError();
+}
+
+// stage 3: a host-memory batch's bytes on their way into HBM
+static int stage_in_out(rcx_ctx* c, const rcx_call& call, batch_state& st)
+{
+    const rcx_batch* b = st.b;
+    hipStream_t s = c->stream;
+    st.d_in = b->in_base; st.d_out = b->out_base;
+    if (b->mem != RCX_MEM_HOST) return RCX_RC_OK;
+    const size_t out_shift = st.mirror ? (size_t)((uintptr_t)st.mirror & 255u) : 0;           // the copy in HBM and the host buffer: the same alignment
+    HIPCHK(c, c->d_in.reserve(st.sp.in_span + 64));
+    HIPCHK(c, c->d_out.reserve(st.sp.out_span + out_shift + 64));
+    if (st.sp.in_span && st.pieces <= 1) HIPCHK(c, hipMemcpyAsync(c->d_in.p, b->in_base, st.sp.in_span, hipMemcpyHostToDevice, s));
+    st.d_in = (const uint8_t*)c->d_in.p;
+    st.d_out = (uint8_t*)c->d_out.p + out_shift;
+    if (st.t.preload_out && st.sp.out_span) HIPCHK(c, hipMemcpyAsync(st.d_out, b->out_base, st.sp.out_span, hipMemcpyHostToDevice, s));
+    // the linked LZ4 decoder reads the dictionaries the caller put in front of the chain heads' slots: those ranges alone travel in
+    // (and only what the chains wrote travels back, copy_back)
+    if (call.link) {
+        const uint32_t* head = call.link->plan->head(); const uint32_t* dict = call.link->plan->dict();
+        for (uint32_t i = 0; i < st.n; i++)
+            if (head[i] == i && dict[i]) {
+                const uint64_t at = b->out_off[i] - dict[i];
+                HIPCHK(c, hipMemcpyAsync(st.d_out + at, b->out_base + at, dict[i], hipMemcpyHostToDevice, s));
+            }
+    }
+    return RCX_RC_OK;
+}
+
+// stage 4: the descriptors, through the page-locked block into HBM
+static int pack_descriptors(rcx_ctx* c, const rcx_call& call, batch_state& st)
+{
+    const rcx_batch* b = st.b;
+    const size_t N = st.n;
+    const size_t desc_bytes = (5 * N + 2 * N) * 8 + 2 * N * 4 + 64;
     HIPCHK(c, c->d_desc.reserve(desc_bytes));
     if (desc_bytes > c->h_desc_cap) {
         if (c->h_desc) (void)hipHostFree(c->h_desc);
@@ -393,350 +481,315 @@ static int run_batch(rcx_ctx* c, int codec, const rcx_batch* b, const uint32_t* 
         HIPCHK(c, hipHostMalloc((void**)&c->h_desc, desc_bytes + desc_bytes / 4, hipHostMallocDefault));
         c->h_desc_cap = desc_bytes + desc_bytes / 4;
     }
-    uint64_t* h64 = (uint64_t*)c->h_desc;
+    uint64_t* h64 = st.h64 = (uint64_t*)c->h_desc;
     memcpy(h64 + 0 * N, b->in_off, N * 8);
     memcpy(h64 + 1 * N, b->in_len, N * 8);
-    if (needs_out) { memcpy(h64 + 2 * N, b->out_off, N * 8); memcpy(h64 + 3 * N, b->out_cap, N * 8); }
+    if (call.needs_out) { memcpy(h64 + 2 * N, b->out_off, N * 8); memcpy(h64 + 3 * N, b->out_cap, N * 8); }
     else memset(h64 + 2 * N, 0, 2 * N * 8);
-    if (n_out) memcpy(h64 + 4 * N, n_out, N * 8); else memset(h64 + 4 * N, 0, N * 8);
-    int32_t* h_status = (int32_t*)(h64 + 7 * N);
-    uint32_t* h_aux = (uint32_t*)(h_status + N);
-    for (size_t i = 0; i < N; i++) h_status[i] = RCX_E_MALFORMED;
-    if (aux_in) memcpy(h_aux, aux_in, N * 4); else memset(h_aux, 0, N * 4);
+    if (call.n_out) memcpy(h64 + 4 * N, call.n_out, N * 8); else memset(h64 + 4 * N, 0, N * 8);
+    st.h_status = (int32_t*)(h64 + 7 * N);
+    st.h_aux = (uint32_t*)(st.h_status + N);
+    for (size_t i = 0; i < N; i++) st.h_status[i] = RCX_E_MALFORMED;
+    if (call.aux_in) memcpy(st.h_aux, call.aux_in, N * 4); else memset(st.h_aux, 0, N * 4);
     memset(h64 + 5 * N, 0, 2 * N * 8);
-    HIPCHK(c, hipMemcpyAsync(c->d_desc.p, c->h_desc, (7 * N) * 8 + 2 * N * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->d_desc.p, c->h_desc, (7 * N) * 8 + 2 * N * 4, hipMemcpyHostToDevice, c->stream));
     uint64_t* d64 = (uint64_t*)c->d_desc.p;
-
-    rcx_kargs k;
-    k.in_base = d_in; k.in_off = d64; k.in_len = d64 + N;
-    k.out_base = d_out; k.out_off = d64 + 2 * N; k.out_cap = d64 + 3 * N;
-    k.n_out = d64 + 4 * N;
-    k.out_len = d64 + 5 * N; k.in_used = d64 + 6 * N;
-    k.status = (int32_t*)(d64 + 7 * N); k.aux = (uint32_t*)(k.status + N);
-    k.nblocks = n;
-    uint64_t sb = rcx_scratch_bytes(codec, n, codec == RCX_BWT_SUFFIXES ? max_in : max_block);
-    if (codec == RCX_DEFLATE_ENCODE || codec == RCX_ZLIB_ENCODE || codec == RCX_GZIP_ENCODE) {      // the staging of the real segments
-        uint64_t segs = 0;
-        for (uint32_t i = 0; i < n; i++) segs += rcx_tu_deflate_encode_segments(b->in_len[i]);
-        sb = param_over > 1 ? rcx_tu_deflate_level_scratch(n, segs) : rcx_tu_deflate_encode_scratch(n, segs);   // (+ chains, parse: levels 2..9)
-    }
-    if (codec == RCX_LZ4_ENCODE && param_over > 0) {                // HC: the chains and parse of the real segments
-        uint64_t segs = 0;
-        for (uint32_t i = 0; i < n; i++) segs += rcx_tu_lz4_hc_segments(b->in_len[i]);
-        sb = rcx_tu_lz4_hc_scratch(n, segs);
-    }
-    if (codec == RCX_DC_ENCODE && param_over > 0) sb = 0;          // withctx: the wave-per-block kernel encodes, no chunk states
-    if (codec == RCX_DC_ENCODE && sb && c->d_scratch.reserve(sb + 64) != hipSuccess) {
-        // the chunk states are optional (37 KiB a block): a batch too large for them falls back to the wave-per-block kernel
-        (void)hipGetLastError();
-        k.scratch = nullptr; k.scratch_bytes = 0;
-    } else {
-        HIPCHK(c, c->d_scratch.reserve(sb + 64));
-        k.scratch = c->d_scratch.p; k.scratch_bytes = c->d_scratch.cap;
-        if (codec == RCX_DC_ENCODE && !sb) { k.scratch = nullptr; k.scratch_bytes = 0; }
-    }
-    k.out_mirror = mirror; k.gate = nullptr; k.gate_host = nullptr; k.gate_seq = 0; k.gate_ticks = 0; k.gate_all = 0;
-    for (int i = 0; i < 15; i++) k.gate_bnd[i] = 0xffffffffu;
-    bool gated = false;
-    if (pieces > 1) {
-        // ONE launch, the input in ranges: the blocks of a range (the first one small: a sixty-fourth of the blocks) start when this
-        // thread has seen the range's copy complete and said so in a page-locked word (k_lz4_decode_v8, `gate`).  A launch per range
-        // was built first and measured: each one ends with the link drained and begins with nothing to send, 5.9 ms for three
-        // growing ranges, 6.6 for eight equal ones, against 7.0 for one launch behind one copy and 5.6 for this.
-        // A range's compressed bytes are the span from its lowest to its highest input byte, widened to whole 256-byte lines of the
-        // staging buffer (a line two ranges share is complete the first time anybody reads it; what the widening copies early are the
-        // caller's own bytes).  Blocks that do not lie in index order make the spans overlap: more than a quarter of the input twice and
-        // the call goes back to one copy in front of the launch.  A block whose input does not arrive in gate_ticks gives up with
-        // RCX_ST_GATE and is decoded by a second launch below (the copies cannot be held up by the waiting blocks as long as a copy
-        // engine moves them; a copy done by a kernel could be, and then this is what ends the wait).
-        std::vector<uint32_t> bnd(1, 0);
-        const uint32_t fdiv = ((c->param[codec] >> 16) & 255u) ? ((c->param[codec] >> 16) & 255u) : 64u;       // (tuning)
-        const uint32_t first = n / fdiv > 64u ? n / fdiv : 64u;
-        for (uint32_t pc = 1; pc < pieces; pc++) {
-            const uint32_t at = first + (uint32_t)((uint64_t)(n - first) * (pc - 1) / (pieces - 1));
-            if (at > bnd.back() && at < n) bnd.push_back(at);
-        }
-        bnd.push_back(n);
-        pieces = (uint32_t)bnd.size() - 1;
-        std::vector<uint64_t> lo(pieces, ~0ull), hi(pieces, 0);
-        uint64_t moved = 0;
-        for (uint32_t pc = 0; pc < pieces; pc++) {
-            for (uint32_t i = bnd[pc]; i < bnd[pc + 1]; i++) {
-                if (!b->in_len[i]) continue;
-                if (b->in_off[i] < lo[pc]) lo[pc] = b->in_off[i];
-                if (b->in_off[i] + b->in_len[i] > hi[pc]) hi[pc] = b->in_off[i] + b->in_len[i];
-            }
-            if (hi[pc] > lo[pc]) {
-                lo[pc] &= ~255ull;
-                hi[pc] = (hi[pc] + 255ull) & ~255ull; if (hi[pc] > in_span) hi[pc] = in_span;
-                moved += hi[pc] - lo[pc];
-            }
-        }
-        if (pieces <= 1 || moved > in_span + in_span / 4) {
-            pieces = 1;
-            if (in_span) HIPCHK(c, hipMemcpyAsync(c->d_in.p, b->in_base, in_span, hipMemcpyHostToDevice, s));
-        } else {
-            if (!c->copy_stream) {
-                // a stream of ANOTHER priority than the launch's: HIP hands its few hardware queues to the streams of one priority in
-                // turn, and a copy stream that shares the launch's queue stands behind the launch it is meant to feed (every gate ran into
-                // its limit for one context in two: 66 ms a call).  The LOWEST priority: it carries copy-engine work only, and the
-                // high-priority queues stay with whoever uses them for kernels (pipeline.PipelineLanes keeps its two lanes apart that way)
-                int least = 0, greatest = 0;
-                HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-                HIPCHK(c, hipStreamCreateWithPriority(&c->copy_stream, hipStreamNonBlocking, least));
-            }
-            while (c->piece_ev.size() < pieces) { hipEvent_t e; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->piece_ev.push_back(e); }
-            const uint32_t seq = ++c->gate_seq ? c->gate_seq : ++c->gate_seq;       // (never 0)
-            if (!c->h_gate) HIPCHK(c, hipHostMalloc((void**)&c->h_gate, 64, hipHostMallocDefault));
-            // the gate words hold anything BUT this call's number before the launch: recycled page-locked or device memory is not zero, and a
-            // stale word that happened to equal `seq` would let a range's blocks read input that has not arrived
-            for (int w = 0; w < 16; w++) __atomic_store_n((volatile uint32_t*)(c->h_gate + w), seq - 1u, __ATOMIC_RELAXED);
-            HIPCHK(c, c->d_gate.reserve(64));
-            HIPCHK(c, hipMemsetAsync(c->d_gate.p, 0, 64, s));                        // (0 is never a call's number; in front of the launch on its stream)
-            {
-                hipPointerAttribute_t ga;
-                HIPCHK(c, hipPointerGetAttributes(&ga, c->h_gate));
-                k.gate_host = (const uint32_t*)ga.devicePointer;
-            }
-            k.gate = (uint32_t*)c->d_gate.p; k.gate_seq = seq;
-            for (uint32_t pc = 1; pc < pieces; pc++) k.gate_bnd[pc - 1] = bnd[pc];
-            const uint64_t ticks = 1000000ull + in_span / 50ull;                   // 10 ms + the input at 5 GB/s (100 MHz ticks)
-            k.gate_ticks = ticks > 0xffffffffull ? 0xffffffffu : (uint32_t)ticks;
-            // (range 0 waits at a gate like the others: the launch is on its way to the device while the first bytes are)
-            k.gate_all = 1;
-            // a failure behind the launch must not leave it spinning at its gates under the next call's copies: open every gate (the blocks
-            // decode whatever has arrived; the call fails anyway), drain both streams, then return
-            bool launched = false;
-            auto bail = [&](hipError_t e, const char* what) {
-                c->err = std::string(what) + ": " + hipGetErrorString(e);
-                (void)hipGetLastError();
-                if (launched) for (int w = 0; w < 16; w++) __atomic_store_n((volatile uint32_t*)(c->h_gate + w), seq, __ATOMIC_RELEASE);
-                (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamSynchronize(s);
-                return RCX_RC_HIP_ERROR;
-            };
-            for (uint32_t pc = 0; pc < pieces; pc++) {
-                hipError_t e = hipSuccess;
-                if (hi[pc] > lo[pc]) e = hipMemcpyAsync((uint8_t*)c->d_in.p + lo[pc], b->in_base + lo[pc], hi[pc] - lo[pc], hipMemcpyHostToDevice, c->copy_stream);
-                if (e != hipSuccess) return bail(e, "host path: range copy");
-                if ((e = hipEventRecord(c->piece_ev[pc], c->copy_stream)) != hipSuccess) return bail(e, "host path: event record");
-                if (pc == 0) {
-                    const int rcg = launch_codec(c, codec, k, param_over);
-                    if (rcg) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamSynchronize(s); return rcg; }
-                    launched = true;
-                }
-            }
-            // this thread tells the launch what has arrived (a word copied in behind each range would be the natural signal; such a small
-            // copy is done by a kernel, and a kernel does not run while every slot of the device holds a waiting block: built, measured --
-            // every gate ran into its time limit)
-            for (uint32_t pc = 0; pc < pieces; pc++) {
-                const hipError_t e = hipEventSynchronize(c->piece_ev[pc]);
-                if (e != hipSuccess) return bail(e, "host path: event wait");
-                __atomic_store_n((volatile uint32_t*)(c->h_gate + pc), seq, __ATOMIC_RELEASE);
-            }
-            gated = true;
-        }
-    }
-    if (!gated) {
-        int rc = launch_codec(c, codec, k, param_over);
-        if (rc) return rc;
-    }
-    if (mirror && !k.out_mirror) mirror = nullptr;                      // the launch says it did not store into the caller's buffer after all: the plain copy below
-    HIPCHK(c, hipMemcpyAsync(h64 + 5 * N, d64 + 5 * N, 2 * N * 8 + 2 * N * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (gated) {
-        HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-        bool again = false;
-        for (size_t i = 0; i < N && !again; i++) again = h_status[i] == (int32_t)RCX_ST_GATE;
-        if (again && codec != RCX_LZ4_DECODE) {                 // (the inflate path's second pass and trailer check passed these streams by: the whole batch again, behind one copy)
-            c->gate_bad = true; c->gate_bad_calls = GATE_RETRY;
-            return run_batch(c, codec, b, aux_in, aux_out, n_out, needs_out, param_over);
-        }
-        if (again) {
-            c->gate_bad = true; c->gate_bad_calls = GATE_RETRY;
-            k.gate = nullptr;
-            rcx_tu_lz4_decode_mirror_again(s, k);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(h64 + 5 * N, d64 + 5 * N, 2 * N * 8 + 2 * N * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
-        }
-    }
-    if (mirror && inf_mirror && k.scratch) {
-        // the streams the first pass handed back were decoded into HBM alone: a few, one copy each; many (a batch of corrupted streams), the span
-        const uint8_t* marks = (const uint8_t*)k.scratch + (codec == RCX_GZIP_DECODE ? rcx_tu_gzip_marks_offset(n) : rcx_tu_inflate_marks_offset(n));
-        uint32_t nfb = 0;
-        HIPCHK(c, hipMemcpy(&nfb, marks, 4, hipMemcpyDeviceToHost));
-        if (nfb) {
-            const uint64_t* ol = h64 + 5 * N;
-            if (nfb > n / 8u + 16u) {
-                uint64_t used_span = 0;
-                for (uint32_t i = 0; i < n; i++) {
-                    const uint64_t l = ol[i] < b->out_cap[i] ? ol[i] : b->out_cap[i];
-                    if (l && b->out_off[i] + l > used_span) used_span = b->out_off[i] + l;
-                }
-                if (used_span) HIPCHK(c, hipMemcpy(b->out_base, d_out, used_span, hipMemcpyDeviceToHost));
-            } else {
-                std::vector<uint8_t> fb(n);
-                HIPCHK(c, hipMemcpy(fb.data(), marks + 64, n, hipMemcpyDeviceToHost));
-                for (uint32_t i = 0; i < n; i++) {
-                    const uint64_t l = ol[i] < b->out_cap[i] ? ol[i] : b->out_cap[i];
-                    if (fb[i] && l) HIPCHK(c, hipMemcpyAsync(b->out_base + b->out_off[i], d_out + b->out_off[i], l, hipMemcpyDeviceToHost, s));
-                }
-                HIPCHK(c, hipStreamSynchronize(s));
-            }
-        }
-    }
-    if (b->mem == RCX_MEM_HOST && out_span && !mirror) {
-        // only what was produced travels back: the span up to the last byte any block wrote, not the slots' capacity
-        uint64_t used_span = 0;
-        const uint64_t* ol = h64 + 5 * N;
-        for (uint32_t i = 0; i < n; i++) {
-            const uint64_t l = ol[i] < b->out_cap[i] ? ol[i] : b->out_cap[i];
-            if (l && b->out_off[i] + l > used_span) used_span = b->out_off[i] + l;
-        }
-        if (codec == RCX_LZ4_DECODE_LINKED) {
-            // a chain's bytes lie behind its head's out_off, as many as its blocks' out_len add up to; nothing else of the caller's
-            // buffer changes (the staging buffer never held the caller's bytes between the slots).  Chains that touch travel as one copy.
-            used_span = 0;
-            uint64_t lo = 0, hi = 0;
-            for (uint32_t i = 0; i < n;) {
-                uint64_t sum = 0;
-                uint32_t j = i;
-                do { sum += ol[j]; j++; } while (j < n && c->link.h_head[j] == i);
-                if (sum > b->out_cap[i]) sum = b->out_cap[i];
-                // (a chain whose last block failed may have written part of that block behind the sum: inside its slot, not reported)
-                if (sum && b->out_off[i] == hi) hi += sum;
-                else if (sum) {
-                    if (hi > lo) HIPCHK(c, hipMemcpyAsync(b->out_base + lo, d_out + lo, hi - lo, hipMemcpyDeviceToHost, s));
-                    lo = b->out_off[i]; hi = lo + sum;
-                }
-                i = j;
-            }
-            if (hi > lo) HIPCHK(c, hipMemcpyAsync(b->out_base + lo, d_out + lo, hi - lo, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
-        }
-        if (used_span) HIPCHK(c, hipMemcpy(b->out_base, d_out, used_span, hipMemcpyDeviceToHost));
-    }
-    if (b->out_len) memcpy(b->out_len, h64 + 5 * N, N * 8);
-    if (b->in_used) memcpy(b->in_used, h64 + 6 * N, N * 8);
-    memcpy(b->status, h_status, N * 4);
-    if (aux_out) memcpy(aux_out, h_aux, N * 4);
+    int32_t* d_status = (int32_t*)(d64 + 7 * N);
+    st.dv = {st.d_in, d64, d64 + N, st.d_out, d64 + 2 * N, d64 + 3 * N, d64 + 5 * N, d64 + 6 * N, d_status, (uint32_t*)(d_status + N), st.n};
+    st.d_n_out = d64 + 4 * N;
     return RCX_RC_OK;
 }
 
-extern "C" int rcx_lz4_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_LZ4_DECODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_lz4_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_LZ4_ENCODE, b, nullptr, nullptr, nullptr, true, 0); }
+// stage 5: scratch, by the codec's rule
+static int reserve_scratch(rcx_ctx* c, const rcx_call& call, batch_state& st)
+{
+    const rcx_batch* b = st.b;
+    const uint32_t n = st.n;
+    uint64_t sb = 0, segs = 0;
+    switch (st.t.scratch) {
+    case SCRATCH_BY_CODEC: sb = rcx_scratch_bytes(call.codec, n, call.codec == RCX_BWT_SUFFIXES ? st.sp.max_in : st.sp.max_block); break;
+    case SCRATCH_DEFLATE_SEGS: case SCRATCH_DEFLATE_LEVEL_SEGS:
+        for (uint32_t i = 0; i < n; i++) segs += rcx_tu_deflate_encode_segments(b->in_len[i]);
+        sb = st.t.scratch == SCRATCH_DEFLATE_LEVEL_SEGS ? rcx_tu_deflate_level_scratch(n, segs) : rcx_tu_deflate_encode_scratch(n, segs);
+        break;
+    case SCRATCH_HC_SEGS:
+        for (uint32_t i = 0; i < n; i++) segs += rcx_tu_lz4_hc_segments(b->in_len[i]);
+        sb = rcx_tu_lz4_hc_scratch(n, segs);
+        break;
+    case SCRATCH_DC_OPTIONAL:                                       // withctx: the wave-per-block kernel encodes, no chunk states
+        sb = call.param ? 0 : rcx_scratch_bytes(call.codec, n, st.sp.max_block);
+        break;
+    }
+    st.scratch = nullptr; st.scratch_bytes = 0;
+    if (st.t.scratch == SCRATCH_DC_OPTIONAL && sb && c->d_scratch.reserve(sb + 64) != hipSuccess) {
+        // the chunk states are optional (37 KiB a block): a batch too large for them falls back to the wave-per-block kernel
+        (void)hipGetLastError();
+        return RCX_RC_OK;
+    }
+    HIPCHK(c, c->d_scratch.reserve(sb + 64));
+    if (st.t.scratch != SCRATCH_DC_OPTIONAL || sb) { st.scratch = c->d_scratch.p; st.scratch_bytes = c->d_scratch.cap; }
+    return RCX_RC_OK;
+}
+
+// stage 6, ranges: the copy stream, the events and the gate words of this call
+static int open_gates(rcx_ctx* c, const batch_state& st, gate_args& g)
+{
+    if (!c->copy_stream) {
+        // a stream of ANOTHER priority than the launch's: HIP hands its few hardware queues to the streams of one priority in
+        // turn, and a copy stream that shares the launch's queue stands behind the launch it is meant to feed (every gate ran into
+        // its limit for one context in two: 66 ms a call).  The LOWEST priority: it carries copy-engine work only, and the
+        // high-priority queues stay with whoever uses them for kernels (pipeline.PipelineLanes keeps its two lanes apart that way)
+        int least = 0, greatest = 0;
+        HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCHK(c, hipStreamCreateWithPriority(&c->copy_stream, hipStreamNonBlocking, least));
+    }
+    while (c->piece_ev.size() < st.pieces) { hipEvent_t e; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->piece_ev.push_back(e); }
+    const uint32_t seq = ++c->gate_seq ? c->gate_seq : ++c->gate_seq;       // (never 0)
+    if (!c->h_gate) HIPCHK(c, hipHostMalloc((void**)&c->h_gate, 64, hipHostMallocDefault));
+    // the gate words hold anything BUT this call's number before the launch: recycled page-locked or device memory is not zero, and a
+    // stale word that happened to equal `seq` would let a range's blocks read input that has not arrived
+    for (int w = 0; w < 16; w++) __atomic_store_n((volatile uint32_t*)(c->h_gate + w), seq - 1u, __ATOMIC_RELAXED);
+    HIPCHK(c, c->d_gate.reserve(64));
+    HIPCHK(c, hipMemsetAsync(c->d_gate.p, 0, 64, c->stream));                // (0 is never a call's number; in front of the launch on its stream)
+    hipPointerAttribute_t ga;
+    HIPCHK(c, hipPointerGetAttributes(&ga, c->h_gate));
+    const uint64_t ticks = 1000000ull + st.sp.in_span / 50ull;               // 10 ms + the input at 5 GB/s (100 MHz ticks)
+    g = {(uint32_t*)c->d_gate.p, (const uint32_t*)ga.devicePointer, seq, ticks > 0xffffffffull ? 0xffffffffu : (uint32_t)ticks, &st.ranges};
+    return RCX_RC_OK;
+}
+
+// stage 6, ranges: ONE launch, the input in ranges.  The blocks of a range (the first one small: a sixty-fourth of the blocks) start when
+// this thread has seen the range's copy complete and said so in a page-locked word (k_lz4_decode_v8, `gate`).  A launch per range
+// was built first and measured: each one ends with the link drained and begins with nothing to send, 5.9 ms for three
+// growing ranges, 6.6 for eight equal ones, against 7.0 for one launch behind one copy and 5.6 for this.
+// A block whose input does not arrive in gate_ticks gives up with RCX_ST_GATE and is decoded by a second launch (run_batch; the copies
+// cannot be held up by the waiting blocks as long as a copy engine moves them; a copy done by a kernel could be, and then this is what
+// ends the wait).
+static int launch_gated(rcx_ctx* c, const rcx_call& call, batch_state& st)
+{
+    const rcx_batch* b = st.b;
+    hipStream_t s = c->stream;
+    const uint32_t seq = st.k.gate_seq;
+    // a failure behind the launch must not leave it spinning at its gates under the next call's copies: open every gate (the blocks
+    // decode whatever has arrived; the call fails anyway), drain both streams, then return
+    bool launched = false;
+    auto bail = [&](hipError_t e, const char* what) {
+        c->err = std::string(what) + ": " + hipGetErrorString(e);
+        (void)hipGetLastError();
+        if (launched) for (int w = 0; w < 16; w++) __atomic_store_n((volatile uint32_t*)(c->h_gate + w), seq, __ATOMIC_RELEASE);
+        (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamSynchronize(s);
+        return RCX_RC_HIP_ERROR;
+    };
+    for (uint32_t pc = 0; pc < st.pieces; pc++) {
+        const uint64_t lo = st.ranges.lo[pc], hi = st.ranges.hi[pc];
+        hipError_t e = hipSuccess;
+        if (hi > lo) e = hipMemcpyAsync((uint8_t*)c->d_in.p + lo, b->in_base + lo, hi - lo, hipMemcpyHostToDevice, c->copy_stream);
+        if (e != hipSuccess) return bail(e, "host path: range copy");
+        if ((e = hipEventRecord(c->piece_ev[pc], c->copy_stream)) != hipSuccess) return bail(e, "host path: event record");
+        if (pc == 0) {
+            const int rcg = launch_codec(c, call, st.k);
+            if (rcg) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamSynchronize(s); return rcg; }
+            launched = true;
+        }
+    }
+    // this thread tells the launch what has arrived (a word copied in behind each range would be the natural signal; such a small
+    // copy is done by a kernel, and a kernel does not run while every slot of the device holds a waiting block: built, measured --
+    // every gate ran into its time limit)
+    for (uint32_t pc = 0; pc < st.pieces; pc++) {
+        const hipError_t e = hipEventSynchronize(c->piece_ev[pc]);
+        if (e != hipSuccess) return bail(e, "host path: event wait");
+        __atomic_store_n((volatile uint32_t*)(c->h_gate + pc), seq, __ATOMIC_RELEASE);
+    }
+    st.gated = true;
+    return RCX_RC_OK;
+}
+
+// stage 6: the launch, behind one copy of the input or with the input in ranges under it
+static int launch(rcx_ctx* c, const rcx_call& call, batch_state& st)
+{
+    if (st.pieces > 1 && !rcx_plan_ranges(st.n, st.pieces, (c->param[call.codec] >> 16) & 255u, st.b->in_off, st.b->in_len, st.sp.in_span, st.ranges)) {
+        st.pieces = 1;                                                 // (too few ranges, or ranges that overlap: rcx_plan.h)
+        if (st.sp.in_span) HIPCHK(c, hipMemcpyAsync(c->d_in.p, st.b->in_base, st.sp.in_span, hipMemcpyHostToDevice, c->stream));
+    }
+    gate_args g = {};
+    if (st.pieces > 1) { st.pieces = st.ranges.pieces(); STAGE(open_gates(c, st, g)); }
+    st.k = make_kargs(st.dv, st.d_n_out, st.scratch, st.scratch_bytes, st.mirror, st.pieces > 1 ? &g : nullptr);
+    STAGE(st.pieces > 1 ? launch_gated(c, call, st) : launch_codec(c, call, st.k));
+    if (st.mirror && !st.k.out_mirror) st.mirror = nullptr;           // the launch says it did not store into the caller's buffer after all: the plain copy in copy_back
+    return RCX_RC_OK;
+}
+
+// stage 7: the per-block results; true in `late` when a block's input did not arrive in time (a gated launch alone)
+static int fetch_results(rcx_ctx* c, batch_state& st, bool& late)
+{
+    const size_t N = st.n;
+    HIPCHK(c, hipMemcpyAsync(st.h64 + 5 * N, st.dv.out_len, 2 * N * 8 + 2 * N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    late = false;
+    if (!st.gated) return RCX_RC_OK;
+    HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+    for (size_t i = 0; i < N && !late; i++) late = st.h_status[i] == (int32_t)RCX_ST_GATE;
+    return RCX_RC_OK;
+}
+
+// stage 9, a mirrored inflate: the streams the first pass handed back were decoded into HBM alone -- a few, one copy each; many (a
+// batch of corrupted streams), the span
+static int copy_back_handed_back(rcx_ctx* c, const rcx_call& call, batch_state& st)
+{
+    const rcx_batch* b = st.b;
+    const uint32_t n = st.n;
+    const uint8_t* marks = (const uint8_t*)st.k.scratch + (call.codec == RCX_GZIP_DECODE ? rcx_tu_gzip_marks_offset(n) : rcx_tu_inflate_marks_offset(n));
+    uint32_t nfb = 0;
+    HIPCHK(c, hipMemcpy(&nfb, marks, 4, hipMemcpyDeviceToHost));
+    if (!nfb) return RCX_RC_OK;
+    const uint64_t* ol = st.out_len();
+    if (nfb > n / 8u + 16u) {
+        const uint64_t used_span = rcx_plan_used_span(n, b->out_off, b->out_cap, ol);
+        if (used_span) HIPCHK(c, hipMemcpy(b->out_base, st.d_out, used_span, hipMemcpyDeviceToHost));
+        return RCX_RC_OK;
+    }
+    std::vector<uint8_t> fb(n);
+    HIPCHK(c, hipMemcpy(fb.data(), marks + 64, n, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t l = ol[i] < b->out_cap[i] ? ol[i] : b->out_cap[i];
+        if (fb[i] && l) HIPCHK(c, hipMemcpyAsync(b->out_base + b->out_off[i], st.d_out + b->out_off[i], l, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RCX_RC_OK;
+}
+
+// stage 9: the output bytes of a host-memory batch (unless the launch stored them itself), then the per-block results
+static int copy_back(rcx_ctx* c, const rcx_call& call, batch_state& st)
+{
+    const rcx_batch* b = st.b;
+    const size_t N = st.n;
+    if (st.mirror && st.t.back == BACK_INFLATE && st.k.scratch) STAGE(copy_back_handed_back(c, call, st));
+    if (b->mem == RCX_MEM_HOST && st.sp.out_span && !st.mirror) {
+        if (st.t.back == BACK_CHAINS) {
+            // nothing else of the caller's buffer changes (the staging buffer never held the caller's bytes between the slots)
+            for (const auto& r : rcx_plan_chain_copies(st.n, call.link->plan->head(), b->out_off, b->out_cap, st.out_len()))
+                HIPCHK(c, hipMemcpyAsync(b->out_base + r.first, st.d_out + r.first, r.second - r.first, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        } else {
+            const uint64_t used_span = rcx_plan_used_span(st.n, b->out_off, b->out_cap, st.out_len());
+            if (used_span) HIPCHK(c, hipMemcpy(b->out_base, st.d_out, used_span, hipMemcpyDeviceToHost));
+        }
+    }
+    if (b->out_len) memcpy(b->out_len, st.h64 + 5 * N, N * 8);
+    if (b->in_used) memcpy(b->in_used, st.h64 + 6 * N, N * 8);
+    memcpy(b->status, st.h_status, N * 4);
+    if (call.aux_out) memcpy(call.aux_out, st.h_aux, N * 4);
+    return RCX_RC_OK;
+}
+
+static int run_batch(rcx_ctx* c, const rcx_call& call, const rcx_batch* b)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    batch_state st;
+    STAGE(check_batch(c, call, b, st));
+    if (st.n == 0) return RCX_RC_OK;
+    for (;;) {
+        bool late = false;
+        decide_mirror(c, call, st);
+        STAGE(stage_in_out(c, call, st));
+        STAGE(pack_descriptors(c, call, st));
+        STAGE(reserve_scratch(c, call, st));
+        STAGE(launch(c, call, st));
+        STAGE(fetch_results(c, st, late));
+        if (!late) break;
+        // stage 8: a gate ran into its limit.  The next GATE_RETRY calls take one copy in front of the launch (decide_mirror)
+        c->gate_bad = true; c->gate_bad_calls = GATE_RETRY;
+        if (call.codec == RCX_LZ4_DECODE) {                      // the blocks that gave up, by a second launch
+            st.k.gate = nullptr; st.gated = false;
+            rcx_tu_lz4_decode_mirror_again(c->stream, st.k);
+            HIPCHK(c, hipGetLastError());
+            STAGE(fetch_results(c, st, late));
+            break;
+        }
+        // (the inflate path's second pass and trailer check passed these streams by: the whole batch again, behind one copy -- gate_bad
+        //  keeps this second pass from ranges, so there is no third)
+    }
+    return copy_back(c, call, st);
+}
+
+extern "C" int rcx_lz4_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_LZ4_DECODE), b); }
+extern "C" int rcx_lz4_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_LZ4_ENCODE, 0), b); }
 extern "C" int rcx_lz4_encode_hc_batch(rcx_ctx* c, const rcx_batch* b, int level)
 {
     if (!c) return RCX_RC_BAD_ARG;
     if (level < 1 || level > 12) { c->err = "lz4 hc: level must be 1..12"; return RCX_RC_BAD_ARG; }
-    return run_batch(c, RCX_LZ4_ENCODE, b, nullptr, nullptr, nullptr, true, level);
+    return run_batch(c, call_of(RCX_LZ4_ENCODE, (uint32_t)level), b);
 }
-extern "C" int rcx_inflate_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, RCX_INFLATE, b, nullptr, flags, nullptr, true); }
-extern "C" int rcx_zlib_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, RCX_ZLIB_DECODE, b, nullptr, flags, nullptr, true); }
-extern "C" int rcx_adler32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* adler) { return run_batch(c, RCX_ADLER32, b, nullptr, adler, nullptr, false); }
-extern "C" int rcx_crc32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* crc) { return run_batch(c, RCX_CRC32, b, nullptr, crc, nullptr, false); }
+extern "C" int rcx_inflate_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, call_of(RCX_INFLATE, 0, nullptr, flags), b); }
+extern "C" int rcx_zlib_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, call_of(RCX_ZLIB_DECODE, 0, nullptr, flags), b); }
+extern "C" int rcx_adler32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* adler) { return run_batch(c, call_of(RCX_ADLER32, 0, nullptr, adler), b); }
+extern "C" int rcx_crc32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* crc) { return run_batch(c, call_of(RCX_CRC32, 0, nullptr, crc), b); }
 extern "C" int rcx_xxh32_batch(rcx_ctx* c, const rcx_batch* b, uint32_t seed, uint32_t* hash)
 {
     if (!c) return RCX_RC_BAD_ARG;
     if (b && b->nblocks && !hash) { c->err = "xxh32: null hash array"; return RCX_RC_BAD_ARG; }
-    return run_batch(c, RCX_XXH32, b, nullptr, hash, nullptr, false, (int64_t)seed);
+    rcx_call call = call_of(RCX_XXH32, 0, nullptr, hash);
+    call.seed = seed;
+    return run_batch(c, call, b);
 }
-// The chains are laid out on the host -- every block's head, its depth, the blocks sorted by depth -- and the batch goes through
-// run_batch like any other: launch_codec issues one launch per depth (k_lz4_linked.hip).  A linked block's out_off / out_cap are the
-// caller's to leave unset: the batch run_batch sees has 0 / 0 there.
+// The chains are laid out on the host -- every block's head, its depth, the blocks sorted by depth (rcx_plan.h) -- and the batch goes
+// through run_batch like any other: launch_codec issues one launch per depth (k_lz4_linked.hip).  A linked block's out_off / out_cap
+// are the caller's to leave unset: the batch run_batch sees has 0 / 0 there.
 extern "C" int rcx_lz4_decode_linked_batch(rcx_ctx* c, const rcx_batch* b, const uint8_t* link, const uint64_t* dict_len)
 {
     if (!c) return RCX_RC_BAD_ARG;
     if (!b || (b->nblocks && (!b->out_off || !b->out_cap))) { c->err = "null descriptor array"; return RCX_RC_BAD_ARG; }
     const uint32_t n = b->nblocks;
     if (n == 0) return RCX_RC_OK;
-    if (link && link[0]) { c->err = "lz4 linked decode: block 0 cannot continue a chain"; return RCX_RC_BAD_ARG; }
-    std::vector<uint64_t> ooff(n), ocap(n);
-    std::vector<uint32_t> tab(3 * (size_t)n), depth(n), rounds(2, 0);
-    uint32_t* order = tab.data(); uint32_t* head = order + n; uint32_t* dict = head + n;
-    uint32_t nrounds = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const bool cont = link && link[i];
-        head[i] = cont ? head[i - 1] : i;
-        depth[i] = cont ? depth[i - 1] + 1 : 0;
-        if (depth[i] + 1 > nrounds) nrounds = depth[i] + 1;
-        ooff[i] = cont ? 0 : b->out_off[i];
-        ocap[i] = cont ? 0 : b->out_cap[i];
-        uint64_t d = (!cont && dict_len) ? dict_len[i] : 0;
-        if (d > ooff[i]) { c->err = "block " + std::to_string(i) + ": dict_len reaches below out_base"; return RCX_RC_BAD_ARG; }
-        dict[i] = (uint32_t)(d > 65536u ? 65536u : d);
-    }
-    rounds.assign(nrounds + 2, 0);                              // counting sort by depth
-    for (uint32_t i = 0; i < n; i++) rounds[depth[i] + 2]++;
-    for (uint32_t r = 2; r < nrounds + 2; r++) rounds[r] += rounds[r - 1];
-    for (uint32_t i = 0; i < n; i++) order[rounds[depth[i] + 1]++] = i;
+    rcx_chain_plan plan;
+    if (!rcx_plan_chains(n, link, dict_len, b->out_off, b->out_cap, plan, c->err)) return RCX_RC_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t tab_bytes = ((3 * (size_t)n * 4 + 7) & ~(size_t)7);
     HIPCHK(c, c->d_link.reserve(tab_bytes + (size_t)n * 8));
-    HIPCHK(c, hipMemcpyAsync(c->d_link.p, tab.data(), 3 * (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    c->link.order = (const uint32_t*)c->d_link.p; c->link.head = c->link.order + n; c->link.dict = c->link.head + n;
-    c->link.eff = (uint64_t*)((uint8_t*)c->d_link.p + tab_bytes);
-    c->link.rounds_off = rounds.data(); c->link.nrounds = nrounds;
-    c->link.h_head = head; c->link.h_dict = dict;
+    HIPCHK(c, hipMemcpyAsync(c->d_link.p, plan.tab.data(), 3 * (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    const uint32_t* d_tab = (const uint32_t*)c->d_link.p;
+    const link_tables lt = {&plan, d_tab, d_tab + n, d_tab + 2 * (size_t)n, (uint64_t*)((uint8_t*)c->d_link.p + tab_bytes)};
     rcx_batch bb = *b;
-    bb.out_off = ooff.data(); bb.out_cap = ocap.data();
-    const int rc = run_batch(c, RCX_LZ4_DECODE_LINKED, &bb, nullptr, nullptr, nullptr, true);      // (waits for the stream: the tables above may go)
-    c->link = {};
-    return rc;
+    bb.out_off = plan.out_off.data(); bb.out_cap = plan.out_cap.data();
+    rcx_call call = call_of(RCX_LZ4_DECODE_LINKED);
+    call.link = &lt;
+    return run_batch(c, call, &bb);                              // (waits for the stream: the tables above may go)
 }
-extern "C" int rcx_gzip_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, RCX_GZIP_DECODE, b, nullptr, flags, nullptr, true); }
-extern "C" int rcx_deflate_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_DEFLATE_ENCODE, b, nullptr, nullptr, nullptr, true, 1); }
-extern "C" int rcx_zlib_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_ZLIB_ENCODE, b, nullptr, nullptr, nullptr, true, 1); }
-extern "C" int rcx_gzip_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_GZIP_ENCODE, b, nullptr, nullptr, nullptr, true, 1); }
+extern "C" int rcx_gzip_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, call_of(RCX_GZIP_DECODE, 0, nullptr, flags), b); }
+extern "C" int rcx_deflate_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_DEFLATE_ENCODE, 1), b); }
+extern "C" int rcx_zlib_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_ZLIB_ENCODE, 1), b); }
+extern "C" int rcx_gzip_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_GZIP_ENCODE, 1), b); }
 static int deflate_level_batch(rcx_ctx* c, int codec, const rcx_batch* b, int level)
 {
     if (!c) return RCX_RC_BAD_ARG;
     if (level < 1 || level > 9) { c->err = "deflate encode: level must be 1..9"; return RCX_RC_BAD_ARG; }
-    return run_batch(c, codec, b, nullptr, nullptr, nullptr, true, level);
+    return run_batch(c, call_of(codec, (uint32_t)level), b);
 }
 extern "C" int rcx_deflate_encode_level_batch(rcx_ctx* c, const rcx_batch* b, int level) { return deflate_level_batch(c, RCX_DEFLATE_ENCODE, b, level); }
 extern "C" int rcx_zlib_encode_level_batch(rcx_ctx* c, const rcx_batch* b, int level) { return deflate_level_batch(c, RCX_ZLIB_ENCODE, b, level); }
 extern "C" int rcx_gzip_encode_level_batch(rcx_ctx* c, const rcx_batch* b, int level) { return deflate_level_batch(c, RCX_GZIP_ENCODE, b, level); }
-extern "C" int rcx_bwt_forward_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, RCX_BWT_FORWARD, b, nullptr, origin, nullptr, true); }
-extern "C" int rcx_bwt_suffixes_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, RCX_BWT_SUFFIXES, b, nullptr, origin, nullptr, true); }
-extern "C" int rcx_bwt_inversion_table_batch(rcx_ctx* c, const rcx_batch* b, const uint32_t* origin) { return run_batch(c, RCX_BWT_INVERSION_TABLE, b, origin, nullptr, nullptr, true); }
-extern "C" int rcx_bwt_inverse_batch(rcx_ctx* c, const rcx_batch* b, const uint32_t* origin) { return run_batch(c, RCX_BWT_INVERSE, b, origin, nullptr, nullptr, true); }
-extern "C" int rcx_bwt_inverse_minimal_batch(rcx_ctx* c, const rcx_batch* b, const uint32_t* origin) { return run_batch(c, RCX_BWT_INVERSE_MINIMAL, b, origin, nullptr, nullptr, true); }
-extern "C" int rcx_mtf_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_MTF_ENCODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_mtf_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_MTF_DECODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_dc_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_DC_ENCODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_dc_decode_batch(rcx_ctx* c, const rcx_batch* b, const uint64_t* n_out) { return run_batch(c, RCX_DC_DECODE, b, nullptr, nullptr, n_out, true); }
-// the same with the coding contexts behind the payload (include/rcx.h): the kernels' `withctx` rides in the codec's parameter
-extern "C" int rcx_dc_encode_ctx_batch(rcx_ctx* c, const rcx_batch* b)
-{
-    if (!c) return RCX_RC_BAD_ARG;
-    return run_batch(c, RCX_DC_ENCODE, b, nullptr, nullptr, nullptr, true, 1);
-}
-extern "C" int rcx_dc_decode_ctx_batch(rcx_ctx* c, const rcx_batch* b, const uint64_t* n_out)
-{
-    if (!c) return RCX_RC_BAD_ARG;
-    return run_batch(c, RCX_DC_DECODE, b, nullptr, nullptr, n_out, true, 1);
-}
-extern "C" int rcx_ari_byte_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_ARI_BYTE_ENCODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_ari_byte_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_ARI_BYTE_DECODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_ari_binary_encode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t rate)
-{
-    if (!c) return RCX_RC_BAD_ARG;
-    c->param[RCX_ARI_BINARY_ENCODE] = rate;
-    return run_batch(c, RCX_ARI_BINARY_ENCODE, b, nullptr, nullptr, nullptr, true);
-}
-extern "C" int rcx_ari_binary_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t rate)
-{
-    if (!c) return RCX_RC_BAD_ARG;
-    c->param[RCX_ARI_BINARY_DECODE] = rate;
-    return run_batch(c, RCX_ARI_BINARY_DECODE, b, nullptr, nullptr, nullptr, true);
-}
-extern "C" int rcx_ari_proxy_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_ARI_PROXY_ENCODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_ari_proxy_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_ARI_PROXY_DECODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_ari_apm_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_ARI_APM_ENCODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_ari_apm_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_ARI_APM_DECODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_rle_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_RLE_ENCODE, b, nullptr, nullptr, nullptr, true); }
-extern "C" int rcx_rle_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, RCX_RLE_DECODE, b, nullptr, nullptr, nullptr, true); }
+extern "C" int rcx_bwt_forward_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_FORWARD, 0, nullptr, origin), b); }
+extern "C" int rcx_bwt_suffixes_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_SUFFIXES, 0, nullptr, origin), b); }
+extern "C" int rcx_bwt_inversion_table_batch(rcx_ctx* c, const rcx_batch* b, const uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_INVERSION_TABLE, 0, origin), b); }
+extern "C" int rcx_bwt_inverse_batch(rcx_ctx* c, const rcx_batch* b, const uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_INVERSE, 0, origin), b); }
+extern "C" int rcx_bwt_inverse_minimal_batch(rcx_ctx* c, const rcx_batch* b, const uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_INVERSE_MINIMAL, 0, origin), b); }
+extern "C" int rcx_mtf_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_MTF_ENCODE), b); }
+extern "C" int rcx_mtf_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_MTF_DECODE), b); }
+// the DC codecs' parameter is the kernels' `withctx`: the coding contexts behind the payload (include/rcx.h)
+extern "C" int rcx_dc_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_DC_ENCODE, 0), b); }
+extern "C" int rcx_dc_decode_batch(rcx_ctx* c, const rcx_batch* b, const uint64_t* n_out) { return run_batch(c, call_of(RCX_DC_DECODE, 0, nullptr, nullptr, n_out), b); }
+extern "C" int rcx_dc_encode_ctx_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_DC_ENCODE, 1), b); }
+extern "C" int rcx_dc_decode_ctx_batch(rcx_ctx* c, const rcx_batch* b, const uint64_t* n_out) { return run_batch(c, call_of(RCX_DC_DECODE, 1, nullptr, nullptr, n_out), b); }
+extern "C" int rcx_ari_byte_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_ARI_BYTE_ENCODE), b); }
+extern "C" int rcx_ari_byte_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_ARI_BYTE_DECODE), b); }
+extern "C" int rcx_ari_binary_encode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t rate) { return run_batch(c, call_of(RCX_ARI_BINARY_ENCODE, rate), b); }
+extern "C" int rcx_ari_binary_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t rate) { return run_batch(c, call_of(RCX_ARI_BINARY_DECODE, rate), b); }
+extern "C" int rcx_ari_proxy_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_ARI_PROXY_ENCODE), b); }
+extern "C" int rcx_ari_proxy_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_ARI_PROXY_DECODE), b); }
+extern "C" int rcx_ari_apm_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_ARI_APM_ENCODE), b); }
+extern "C" int rcx_ari_apm_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_ARI_APM_DECODE), b); }
+extern "C" int rcx_rle_encode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_RLE_ENCODE), b); }
+extern "C" int rcx_rle_decode_batch(rcx_ctx* c, const rcx_batch* b) { return run_batch(c, call_of(RCX_RLE_DECODE), b); }
 
 // ---- more than one device -------------------------------------------------------------------------------------------------
 // RCCL, loaded on first use (librcx.so itself does not link it: the library loads wherever HIP does, and a process that has torch's RCCL
@@ -930,15 +983,18 @@ extern "C" void rcx_partition(const uint64_t* weights, uint32_t nblocks, uint32_
 // one codec's host-descriptor entry point by its number (what rcx_multi_batch runs on a range)
 static int run_codec(rcx_ctx* c, int codec, const rcx_batch* b, const uint32_t* aux_in, uint32_t* aux_out, const uint64_t* n_out)
 {
+    if (codec < 0 || codec >= RCX_CODEC_COUNT) { c->err = "unknown codec"; return RCX_RC_BAD_ARG; }
+    // the parameter of the codec's one-device entry point: LZ4 encode the reference's encoder, DC without contexts (0), DEFLATE level 1;
+    // the ARI binary rate, which those entry points take as an argument, is the context's (rcx_ctx_set_param)
+    uint32_t param = 0;
+    if (codec == RCX_DEFLATE_ENCODE || codec == RCX_ZLIB_ENCODE || codec == RCX_GZIP_ENCODE) param = 1;
+    if (codec == RCX_ARI_BINARY_ENCODE || codec == RCX_ARI_BINARY_DECODE) param = c->param[codec];
     switch (codec) {
-    case RCX_ADLER32: case RCX_CRC32: return run_batch(c, codec, b, nullptr, aux_out, nullptr, false);
-    case RCX_DC_DECODE: if (!n_out) { c->err = "dc decode: n_out missing"; return RCX_RC_BAD_ARG; } return run_batch(c, codec, b, nullptr, nullptr, n_out, true);
+    case RCX_DC_DECODE: if (!n_out) { c->err = "dc decode: n_out missing"; return RCX_RC_BAD_ARG; } return run_batch(c, call_of(codec, param, nullptr, nullptr, n_out), b);
     case RCX_BWT_INVERSE: case RCX_BWT_INVERSE_MINIMAL: case RCX_BWT_INVERSION_TABLE:
         if (!aux_in) { c->err = "bwt inverse: origins missing"; return RCX_RC_BAD_ARG; }
-        return run_batch(c, codec, b, aux_in, nullptr, nullptr, true);
-    default:
-        if (codec < 0 || codec >= RCX_CODEC_COUNT) { c->err = "unknown codec"; return RCX_RC_BAD_ARG; }
-        return run_batch(c, codec, b, nullptr, aux_out, nullptr, true);
+        return run_batch(c, call_of(codec, param, aux_in), b);
+    default: return run_batch(c, call_of(codec, param, nullptr, aux_out), b);
     }
 }
 

@@ -418,3 +418,52 @@ def test_bwt_block_over_the_sorters_limit_gets_its_own_status(ctx):
     assert bytes(got[:5000]) == one.outputs[0] == bytes(got[16384: 16384 + 5000])
     assert int(db.aux[0]) == int(one.aux[0]) == int(db.aux[2])
     assert N.lib().rcx_status_string(N.E_BWT_BLOCK_TOO_LARGE).decode() == "bwt block of 2^28 bytes or more"
+
+
+def test_multi_batch_encoders_ignore_the_context_parameter(ctx):
+    """rcx_multi_batch runs an encoder as its one-device entry point does (include/rcx.h): the level rcx_ctx_set_param left in the
+    set's contexts is rcx_launch_dev's alone.  With 9 set on both contexts, zlib and LZ4 encode over the one device listed twice
+    return the bytes, lengths and statuses of rcx_zlib_encode_batch / rcx_lz4_encode_batch on a plain context (blocks on both sides
+    of the encoders' 64 KiB segment edge), and the caller's bytes between the zlib streams stay as they were; the reference's LZ4
+    encoder promises that of the bytes behind the last stream only (one span travels back)."""
+    import ctypes as C
+    from rust_compress_amd import batch as B, synth
+    L = N.lib()
+    raws = [synth.gen("text", k, 5 + i).tobytes() for i, k in enumerate((0, 1, 3000, 65536, 65537, 140000))]
+    raws += [synth.gen("rand", 5000, 31).tobytes(), synth.gen("rand", 70000, 32).tobytes()]
+    n = len(raws)
+    base, off, lens = B.pack(raws)
+    p = lambda a: a.ctypes.data
+    devs = (C.c_int * 2)(0, 0)
+    h = C.c_void_p()
+    assert L.rcx_multi_create(devs, 2, C.byref(h)) == 0
+    try:
+        for codec, bound, one in ((N.ZLIB_ENCODE, L.rcx_deflate_compression_bound, L.rcx_zlib_encode_batch),
+                                  (N.LZ4_ENCODE, L.rcx_lz4_compression_bound, L.rcx_lz4_encode_batch)):
+            total, ooff, ocap = B.layout([int(bound(len(r))) + 7 for r in raws])
+            res = []
+            for multi in (False, True):
+                out = np.full(total + 64, 0xAA, np.uint8)
+                out_len, in_used, status = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.full(n, -9, np.int32)
+                b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
+                if multi:
+                    for g in range(2):
+                        assert L.rcx_ctx_set_param(L.rcx_multi_ctx(h, g), codec, 9) == 0
+                    assert L.rcx_multi_batch(h, codec, C.byref(b), None, None, None) == 0, L.rcx_multi_last_error(h)
+                else:
+                    assert one(ctx._h, C.byref(b)) == 0, L.rcx_last_error(ctx._h)
+                assert not status.any(), (codec, multi, status)
+                res.append((out, out_len, in_used, status))
+            (o0, l0, u0, s0), (o1, l1, u1, s1) = res
+            assert (l0 == l1).all() and (u0 == u1).all() and (s0 == s1).all(), (codec, l0, l1)
+            keep = np.ones(total + 64, bool)
+            for i in range(n):
+                a, e = int(ooff[i]), int(ooff[i]) + int(l1[i])
+                assert bytes(o1[a:e]) == bytes(o0[a:e]), (codec, i)
+                assert codec != N.ZLIB_ENCODE or zlib.decompress(bytes(o1[a:e])) == raws[i]
+                keep[a:e] = False
+            if codec == N.LZ4_ENCODE:
+                keep[: max(int(o) + int(l) for o, l in zip(ooff, l1))] = False
+            assert (o1[keep] == 0xAA).all(), (codec, "bytes outside the streams changed")
+    finally:
+        L.rcx_multi_destroy(h)
