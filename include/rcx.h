@@ -183,6 +183,24 @@ int rcx_xxh32_batch(rcx_ctx*, const rcx_batch*, uint32_t seed, uint32_t* hash);
  * MI355X, device memory: 4096 independent 64 KiB text blocks 0.943 ms a call (rcx_lz4_decode_batch: 0.501), 256 chains of 16 blocks
  * 10.1 ms.  From host memory only the dictionaries are copied in and only the bytes the chains wrote are copied back. */
 int rcx_lz4_decode_linked_batch(rcx_ctx*, const rcx_batch*, const uint8_t* link, const uint64_t* dict_len);
+/* LZ4 high compression with HISTORY: what writes linked blocks and blocks behind a dictionary.  hist_len is a host array of nblocks
+ * entries, or NULL (= all 0).  Block i is encoded exactly as rcx_lz4_encode_hc_batch encodes it (levels, chain depths, end rules,
+ * statuses, bound, in_used), and its matches may also reach into the hist_len[i] (at most 65536, at most in_off[i]) bytes that lie
+ * directly before in_base + in_off[i] -- the mirror of dict_len above.  The caller put them there; they are read and never written, and
+ * they may be another block's input: in a linked frame block k's history is block k-1, and every block of the frame is encoded at once
+ * (all input is known up front: no rounds, no chains, no launch order).  Of 65536 history bytes the first is out of every match's reach
+ * (65536 counts as 65535).  hist_len[i] > in_off[i] or > 65536 returns RCX_RC_BAD_ARG and rcx_last_error names the block.
+ * No emitted offset exceeds position + hist_len[i] or 65535; no byte in front of the history influences the output; the output is
+ * deterministic and does not depend on the block's place in the batch.  With hist_len NULL or all 0 every result (bytes, out_len,
+ * in_used, status) is rcx_lz4_encode_hc_batch's at the same level.  The blocks decode with rcx_lz4_decode_linked_batch given
+ * dict_len[i] = hist_len[i] and the history in front of the slot.
+ * COST: the hash chains of a history are REBUILT for every block that names it, by one more workgroup per block (one more 64 KiB
+ * segment of 16-bit links per block with history: rcx_lz4_hc_hist_scratch_bytes counts every block with one) -- up to twice the chain
+ * work for linked 64 KiB blocks, 17 times for a 2 KiB record behind a 32 KiB dictionary.  A dictionary's table built once and attached
+ * to many blocks, and history that is not contiguous with the block, are not provided.  benchmarks/lz4_hist_rate.py
+ * measures the rebuild. */
+int rcx_lz4_encode_hc_hist_batch(rcx_ctx*, const rcx_batch*, int level, const uint64_t* hist_len);
+uint64_t rcx_lz4_hc_hist_scratch_bytes(uint32_t nblocks, uint64_t max_block);
 
 /* ---- DEFLATE / zlib / Adler-32 ---------------------------------------------- */
 /* reference: src/flate.rs:195-206,237-246,262-341,343-450 (one RFC-1951 stream
@@ -344,7 +362,7 @@ enum rcx_codec {
 };
 /* Ids of the batch entry points that rcx_launch_dev, rcx_multi_* and rcx_scratch_bytes do not take (enum rcx_codec stays as it is for
  * those): they name the entry point to rcx_ctx_set_variant / rcx_ctx_set_param, neither of which has a setting for them yet. */
-enum rcx_xcodec { RCX_XXH32 = 32, RCX_LZ4_DECODE_LINKED = 33, RCX_XCODEC_END = 34 };
+enum rcx_xcodec { RCX_XXH32 = 32, RCX_LZ4_DECODE_LINKED = 33, RCX_LZ4_ENCODE_HIST = 34, RCX_XCODEC_END = 35 };
 /* scratch bytes (HBM) the codec needs for nblocks blocks of <= max_block bytes.  Required for LZ4 encode, BWT and gzip
  * decode and the DEFLATE / zlib / gzip encoders; for RCX_INFLATE / RCX_ZLIB_DECODE it is what the default (wave-per-stream) decoder needs -- without it
  * rcx_launch_dev falls back to the lane-per-stream kernel (same results, slower on small batches). */

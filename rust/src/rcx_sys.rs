@@ -119,7 +119,8 @@ pub const RCX_CODEC_COUNT: c_int = 29;
 // enum rcx_xcodec: batch entry points outside rcx_launch_dev
 pub const RCX_XXH32: c_int = 32;
 pub const RCX_LZ4_DECODE_LINKED: c_int = 33;
-pub const RCX_XCODEC_END: c_int = 34;
+pub const RCX_LZ4_ENCODE_HIST: c_int = 34;
+pub const RCX_XCODEC_END: c_int = 35;
 
 #[link(name = "rcx")]
 extern "C" {
@@ -140,6 +141,9 @@ extern "C" {
     // ---- the LZ4 frame format's device side (extension): XXH32, block decode with history (linked blocks, dictionaries)
     pub fn rcx_xxh32_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, seed: u32, hash: *mut u32) -> c_int;
     pub fn rcx_lz4_decode_linked_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, link: *const u8, dict_len: *const u64) -> c_int;
+    // ---- LZ4 high compression with history (extension): linked blocks and dictionaries on the encode side
+    pub fn rcx_lz4_encode_hc_hist_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int, hist_len: *const u64) -> c_int;
+    pub fn rcx_lz4_hc_hist_scratch_bytes(nblocks: u32, max_block: u64) -> u64;
     // ---- DEFLATE / zlib / Adler-32 (src/flate.rs, src/zlib.rs, src/checksum/adler.rs) + the gzip extension
     pub fn rcx_inflate_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32) -> c_int;
     pub fn rcx_zlib_decode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32) -> c_int;

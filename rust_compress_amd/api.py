@@ -114,6 +114,46 @@ class Context:
             caps = [max(int(N.lib().rcx_lz4_compression_bound(len(b))), 1) for b in blobs]
         return self._run_host("rcx_lz4_encode_hc_batch", blobs, caps, scalar=int(level))
 
+    def lz4_encode_hc_hist(self, base, in_off, in_len, hist_len, level=9, caps=None):
+        """rcx_lz4_encode_hc_hist_batch over a buffer the caller laid out: block i is base[in_off[i] : in_off[i] + in_len[i]] (base: a
+        numpy uint8 array) and its matches may reach into the hist_len[i] bytes below in_off[i] -- a dictionary put there, or the
+        block before it (linked blocks).  hist_len None: no history."""
+        n = len(in_off)
+        off = np.ascontiguousarray(in_off, np.uint64)
+        lens = np.ascontiguousarray(in_len, np.uint64)
+        if caps is None:
+            caps = [max(int(N.lib().rcx_lz4_compression_bound(int(l))), 1) for l in lens]
+        total, ooff, ocap = B.layout(caps)
+        out = np.zeros(total, dtype=np.uint8)
+        out_len = np.zeros(max(n, 1), np.uint64)
+        in_used = np.zeros(max(n, 1), np.uint64)
+        status = np.zeros(max(n, 1), np.int32)
+        hist = np.ascontiguousarray(hist_len, np.uint64) if hist_len is not None else None
+        if hist is not None and hist.size != n:
+            raise ValueError("hist_len: one entry per block")
+        if base.size == 0:
+            base = np.zeros(1, np.uint8)
+        p = lambda a: a.ctypes.data
+        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
+        self._chk(N.lib().rcx_lz4_encode_hc_hist_batch(self._h, C.byref(b), int(level), C.c_void_p(p(hist) if hist is not None and n else None)))
+        return Result(B.unpack(out, ooff, out_len[:n]), out_len[:n], in_used[:n], status[:n], None)
+
+    def lz4_encode_hc_hist_blocks(self, blobs, histories, level=9, caps=None):
+        """One LZ4 block per blob from the high-compression encoder, with HISTORY: histories[i] (bytes or None; its last 64 KiB count)
+        is put directly in front of blobs[i] in the input buffer and the block's matches may reach into it.  The block decodes behind
+        the same bytes (rcx_lz4_decode_linked_batch with dict_len, or any LZ4 decoder given them as its dictionary)."""
+        if len(histories) != len(blobs):
+            raise ValueError("histories: one entry (bytes or None) per blob")
+        buf, off, hl = bytearray(), [], []
+        for blob, h in zip(blobs, histories):
+            h = bytes(h)[-65536:] if h else b""
+            buf += h
+            off.append(len(buf))
+            hl.append(len(h))
+            buf += bytes(blob)
+        base = np.frombuffer(bytes(buf) + b"\0" * 16, np.uint8)
+        return self.lz4_encode_hc_hist(base, off, [len(b) for b in blobs], hl, level, caps)
+
     def inflate(self, blobs, caps):
         return self._run_host("rcx_inflate_batch", blobs, caps, extra_out=True)
 

@@ -159,6 +159,11 @@ extern "C" uint64_t rcx_lz4_hc_scratch_bytes(uint32_t nblocks, uint64_t max_bloc
 {
     return rcx_tu_lz4_hc_scratch(nblocks, (uint64_t)nblocks * rcx_tu_lz4_hc_segments(max_block));
 }
+// (every block counted with a history: one more segment of links each)
+extern "C" uint64_t rcx_lz4_hc_hist_scratch_bytes(uint32_t nblocks, uint64_t max_block)
+{
+    return rcx_tu_lz4_hc_hist_scratch(nblocks, (uint64_t)nblocks * rcx_tu_lz4_hc_segments(max_block), nblocks);
+}
 
 // ---- scratch requirements ---------------------------------------------------------------------
 extern "C" uint64_t rcx_scratch_bytes(int codec, uint32_t nblocks, uint64_t max_block)
@@ -191,6 +196,7 @@ struct rcx_call {
     bool needs_out;
     uint32_t seed;                       // XXH32
     const link_tables* link;             // linked LZ4 decode, else null
+    uint32_t nhist;                      // LZ4 HC encode with history: the blocks that have one (their lengths are aux_in)
 };
 
 // ---- per-codec traits of the host path ------------------------------------------------------------------------------------------------
@@ -198,6 +204,7 @@ enum mirror_kind { MIRROR_NONE, MIRROR_LZ4, MIRROR_INFLATE };          // may th
 enum scratch_rule { SCRATCH_BY_CODEC,                                  // rcx_scratch_bytes
                     SCRATCH_DEFLATE_SEGS, SCRATCH_DEFLATE_LEVEL_SEGS,  // the staging of the real segments (+ chains, parse: levels 2..9)
                     SCRATCH_HC_SEGS,                                   // HC: the chains and parse of the real segments
+                    SCRATCH_HC_HIST_SEGS,                              // ... and the chains of the real histories
                     SCRATCH_DC_OPTIONAL };                             // chunk states: none with contexts, and none when they cannot be had
 enum back_policy { BACK_USED_SPAN, BACK_INFLATE /* mirrored: the streams the first pass handed back */, BACK_CHAINS };
 struct codec_traits {
@@ -223,6 +230,7 @@ static codec_traits traits_of(int codec, uint32_t param)
         t.preload_out = true; t.scratch = param > 1 ? SCRATCH_DEFLATE_LEVEL_SEGS : SCRATCH_DEFLATE_SEGS; break;
     // (and so does the LZ4 HC encoder: a block's slot holds its bound, more than the block takes)
     case RCX_LZ4_ENCODE: if (param) { t.preload_out = true; t.scratch = SCRATCH_HC_SEGS; } break;
+    case RCX_LZ4_ENCODE_HIST: t.preload_out = true; t.scratch = SCRATCH_HC_HIST_SEGS; break;
     case RCX_DC_ENCODE: t.scratch = SCRATCH_DC_OPTIONAL; break;
     case RCX_LZ4_DECODE_LINKED: t.back = BACK_CHAINS; break;
     case RCX_ADLER32: case RCX_CRC32: case RCX_XXH32: t.needs_out = false; break;
@@ -232,7 +240,7 @@ static codec_traits traits_of(int codec, uint32_t param)
 }
 static rcx_call call_of(int codec, uint32_t param = 0, const uint32_t* aux_in = nullptr, uint32_t* aux_out = nullptr, const uint64_t* n_out = nullptr)
 {
-    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr};
+    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr, 0};
 }
 
 // ---- kernel arguments: built here and nowhere else ---------------------------------------------------------------------------------------
@@ -293,6 +301,10 @@ static int launch_codec(rcx_ctx* c, const rcx_call& call, rcx_kargs& k)
         const uint32_t level = call.param;
         if (level > 12) { c->err = "lz4 encode: level must be 0 (reference encoder) or 1..12 (HC)"; return RCX_RC_BAD_ARG; }
         int rc = level ? rcx_tu_lz4_hc(s, k, (int)level, c->err) : rcx_tu_lz4_encode(s, k, v, c->err);
+        if (rc) return rc;
+        break; }
+    case RCX_LZ4_ENCODE_HIST: {                                  // the codec parameter: the HC level; k.aux: the history lengths
+        int rc = rcx_tu_lz4_hc_hist(s, k, (int)call.param, call.nhist, c->err);
         if (rc) return rc;
         break; }
     case RCX_INFLATE:
@@ -516,6 +528,10 @@ static int reserve_scratch(rcx_ctx* c, const rcx_call& call, batch_state& st)
         for (uint32_t i = 0; i < n; i++) segs += rcx_tu_lz4_hc_segments(b->in_len[i]);
         sb = rcx_tu_lz4_hc_scratch(n, segs);
         break;
+    case SCRATCH_HC_HIST_SEGS:
+        for (uint32_t i = 0; i < n; i++) segs += rcx_tu_lz4_hc_segments(b->in_len[i]);
+        sb = rcx_tu_lz4_hc_hist_scratch(n, segs, call.nhist);
+        break;
     case SCRATCH_DC_OPTIONAL:                                       // withctx: the wave-per-block kernel encodes, no chunk states
         sb = call.param ? 0 : rcx_scratch_bytes(call.codec, n, st.sp.max_block);
         break;
@@ -719,6 +735,28 @@ extern "C" int rcx_lz4_encode_hc_batch(rcx_ctx* c, const rcx_batch* b, int level
     if (!c) return RCX_RC_BAD_ARG;
     if (level < 1 || level > 12) { c->err = "lz4 hc: level must be 1..12"; return RCX_RC_BAD_ARG; }
     return run_batch(c, call_of(RCX_LZ4_ENCODE, (uint32_t)level), b);
+}
+// The history travels in with the input (rcx_plan_spans stages [0, in_span), and a history lies below its block); its lengths go to
+// the kernels as 32-bit words in the descriptors' aux array.
+extern "C" int rcx_lz4_encode_hc_hist_batch(rcx_ctx* c, const rcx_batch* b, int level, const uint64_t* hist_len)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    if (level < 1 || level > 12) { c->err = "lz4 hc: level must be 1..12"; return RCX_RC_BAD_ARG; }
+    rcx_call call = call_of(RCX_LZ4_ENCODE_HIST, (uint32_t)level);
+    if (!hist_len || !b || !b->nblocks) return run_batch(c, call, b);
+    if (!b->in_off) { c->err = "null descriptor array"; return RCX_RC_BAD_ARG; }
+    std::vector<uint32_t> hist(b->nblocks);
+    for (uint32_t i = 0; i < b->nblocks; i++) {
+        if (hist_len[i] > b->in_off[i] || hist_len[i] > 65536) {
+            c->err = "lz4 hc: block " + std::to_string(i) + ": a history of " + std::to_string(hist_len[i]) + " bytes "
+                   + (hist_len[i] > 65536 ? "(at most 65536)" : "does not fit in front of in_off " + std::to_string(b->in_off[i]));
+            return RCX_RC_BAD_ARG;
+        }
+        hist[i] = hist_len[i] > 65535 ? 65535u : (uint32_t)hist_len[i];      // (of 65536 bytes the first is out of every match's reach)
+        call.nhist += hist[i] ? 1u : 0u;
+    }
+    call.aux_in = hist.data();
+    return run_batch(c, call, b);                                // (waits for the stream: the lengths above may go)
 }
 extern "C" int rcx_inflate_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, call_of(RCX_INFLATE, 0, nullptr, flags), b); }
 extern "C" int rcx_zlib_decode_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags) { return run_batch(c, call_of(RCX_ZLIB_DECODE, 0, nullptr, flags), b); }

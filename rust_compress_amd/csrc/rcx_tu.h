@@ -42,6 +42,9 @@ uint64_t rcx_tu_deflate_level_scratch(uint32_t nblocks, uint64_t nsegs);
 int rcx_tu_lz4_hc(hipStream_t s, rcx_kargs& k, int level, std::string& err);
 uint64_t rcx_tu_lz4_hc_scratch(uint32_t nblocks, uint64_t nsegs);
 uint64_t rcx_tu_lz4_hc_segments(uint64_t len);
+// ... with history (k_lz4_hc_hist.hip): k.aux = the history lengths (uint32) or null, nhist = the blocks that have one
+int rcx_tu_lz4_hc_hist(hipStream_t s, rcx_kargs& k, int level, uint32_t nhist, std::string& err);
+uint64_t rcx_tu_lz4_hc_hist_scratch(uint32_t nblocks, uint64_t nsegs, uint64_t nhist);
 // tu_lz4_frame.hip: XXH32 of every block; LZ4 block decode with history (linked blocks, dictionaries), one launch per chain depth
 void rcx_tu_xxh32(hipStream_t s, rcx_kargs& k, uint32_t seed);
 // order[rounds_off[r] .. rounds_off[r + 1]): the blocks at depth r of their chains (rounds_off is a HOST array); head[i]: block i's chain

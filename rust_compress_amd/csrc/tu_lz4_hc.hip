@@ -1,7 +1,10 @@
-// tu_lz4_hc.hip -- the batched LZ4 high-compression block encoder + its launch code (one translation unit).
+// tu_lz4_hc.hip -- the batched LZ4 high-compression block encoder, without and with history, + its launch code (one translation unit).
 #include "rcx_tu.h"
 #include "k_lz4_hc.hip"
+#include "k_lz4_hc_hist.hip"
 
 int rcx_tu_lz4_hc(hipStream_t s, rcx_kargs& k, int level, std::string& err) { return launch_lz4_hc(s, k, level, err); }
 uint64_t rcx_tu_lz4_hc_scratch(uint32_t nblocks, uint64_t nsegs) { return hc_scratch_bytes(nblocks, nsegs); }
 uint64_t rcx_tu_lz4_hc_segments(uint64_t len) { return hc_segments(len); }
+int rcx_tu_lz4_hc_hist(hipStream_t s, rcx_kargs& k, int level, uint32_t nhist, std::string& err) { return launch_lz4_hc_hist(s, k, level, nhist, err); }
+uint64_t rcx_tu_lz4_hc_hist_scratch(uint32_t nblocks, uint64_t nsegs, uint64_t nhist) { return hc_hist_scratch_bytes(nblocks, nsegs, nhist); }

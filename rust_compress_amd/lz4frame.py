@@ -8,8 +8,9 @@ host thread; a batch does not):
     decode_frames(blobs)   every block of every frame through ONE rcx_lz4_decode_linked_batch call (linked blocks and dictionaries
                            are that call's history), every block checksum through one rcx_xxh32_batch call, every content
                            checksum through another
-    encode_frames(blobs)   independent blocks from the greedy encoder (level=None) or the high-compression one (level 1..12),
-                           checksums from rcx_xxh32_batch
+    encode_frames(blobs)   independent blocks from the greedy encoder (level=None) or the high-compression one (level 1..12), or --
+                           with a level -- linked blocks and blocks behind a dictionary (rcx_lz4_encode_hc_hist_batch: every block
+                           of every frame in ONE call); checksums from rcx_xxh32_batch
     Decoder(r) / Encoder(w)   the buffered stream classes in the style of compress.py
 
 There is no CPU path: the parsing is Python, every decoded, encoded or hashed byte comes from the device.
@@ -421,22 +422,61 @@ def _block_size_id(block_size):
     raise ValueError("block_size must be 64 KiB, 256 KiB, 1 MiB or 4 MiB (or the format's id 4..7)")
 
 
-def encode_frames(blobs, level=None, block_size=64 << 10, block_checksum=False, content_checksum=True, content_size=True, ctx=None):
-    """One LZ4 frame per blob, block-independent.  level=None: the greedy block encoder (rcx_lz4_encode_batch); 1..12: the
-    high-compression one (rcx_lz4_encode_hc_batch).  A block that compression does not shrink is stored.  block_size: 64 KiB,
-    256 KiB, 1 MiB or 4 MiB (or the id 4..7).  The header checksum, the optional block checksums (of each block as written) and the
-    optional content checksum come from rcx_xxh32_batch; the frame ends with one EndMark.  Every block of every blob is compressed
-    by one call."""
+def _encode_with_history(ctx, blobs, bmax, level, linked, dct):
+    """Every block of every blob through ONE rcx_lz4_encode_hc_hist_batch call.  The staging buffer holds, linked: each frame as
+    dictionary || blob, and block k's history is what lies in front of it there (the dictionary and the frame's bytes before it, at most
+    64 KiB); independent blocks behind a dictionary: the dictionary in front of every block.  -> the blocks' LZ4 bytes, in order"""
+    buf, off, lens, hist = bytearray(), [], [], []
+    for blob in blobs:
+        if linked:
+            buf += dct
+            start = len(buf)
+            buf += blob
+        for at in range(0, len(blob), bmax):
+            n = min(bmax, len(blob) - at)
+            if linked:
+                off.append(start + at)
+                hist.append(min(DICT_MAX, len(dct) + at))
+            else:
+                buf += dct
+                off.append(len(buf))
+                hist.append(len(dct))
+                buf += blob[at:at + n]
+            lens.append(n)
+    if not off:
+        return []
+    base = np.frombuffer(bytes(buf) + b"\0" * 16, np.uint8)
+    return ctx.lz4_encode_hc_hist(base, off, lens, hist, int(level)).check().outputs
+
+
+def encode_frames(blobs, level=None, block_size=64 << 10, block_checksum=False, content_checksum=True, content_size=True, ctx=None,
+                  linked=False, dictionary=None, dict_id=None):
+    """One LZ4 frame per blob.  level=None: the greedy block encoder (rcx_lz4_encode_batch); 1..12: the high-compression one
+    (rcx_lz4_encode_hc_batch).  A block that compression does not shrink is stored.  block_size: 64 KiB, 256 KiB, 1 MiB or 4 MiB (or
+    the id 4..7).  The header checksum, the optional block checksums (of each block as written) and the optional content checksum
+    come from rcx_xxh32_batch; the frame ends with one EndMark.  Every block of every blob is compressed by one call.
+
+    linked=True writes block-linked frames (what the `lz4` tool writes by default): a block's matches reach up to 64 KiB back into the
+        frame's earlier blocks -- also into a stored one's bytes.  All blocks are still encoded at once: history is input.
+    dictionary: bytes whose last 64 KiB are the history in front of every frame's first block (linked) or of every block
+        (independent); decode_frames and LZ4F_decompress_usingDict want the same bytes.  dict_id: written as the header's dictionary
+        id when given.
+    linked and dictionary need a level (rcx_lz4_encode_hc_hist_batch): the greedy encoder has no history."""
     ctx = ctx or _compress.context()
     bid = _block_size_id(block_size)
     bmax = BLOCK_MAX[bid]
     blobs = [bytes(b) for b in blobs]
+    dct = bytes(dictionary)[-DICT_MAX:] if dictionary else b""
+    if (linked or dct) and level is None:
+        raise ValueError("linked blocks and dictionaries need the high-compression encoder: choose a level from 1 to 12")
     raws, owner = [], []
     for i, blob in enumerate(blobs):
         for at in range(0, len(blob), bmax):
             raws.append(blob[at:at + bmax])
             owner.append(i)
-    if raws:
+    if linked or dct:
+        comp = _encode_with_history(ctx, blobs, bmax, level, linked, dct)
+    elif raws:
         res = (ctx.lz4_encode_blocks(raws) if level is None else ctx.lz4_encode_hc_blocks(raws, int(level))).check()
         comp = res.outputs
     else:
@@ -445,8 +485,10 @@ def encode_frames(blobs, level=None, block_size=64 << 10, block_checksum=False, 
     # descriptors first: their checksums, the blocks' and the contents' go through one call
     descs = []
     for blob in blobs:
-        flg = 0x40 | 0x20 | (0x10 if block_checksum else 0) | (8 if content_size else 0) | (4 if content_checksum else 0)
-        descs.append(bytes([flg, bid << 4]) + (struct.pack("<Q", len(blob)) if content_size else b""))
+        flg = 0x40 | (0 if linked else 0x20) | (0x10 if block_checksum else 0) | (8 if content_size else 0) | (4 if content_checksum else 0) \
+            | (1 if dict_id is not None else 0)
+        descs.append(bytes([flg, bid << 4]) + (struct.pack("<Q", len(blob)) if content_size else b"")
+                     + (struct.pack("<I", dict_id) if dict_id is not None else b""))
     regions = list(descs)
     if block_checksum:
         regions += [w[1] for w in written]
@@ -490,10 +532,14 @@ class Decoder(_compress._BufferedDecoder):
 class Encoder:
     """Collects what is written and, at finish(), writes it to `w` as one standard LZ4 frame (encode_frames' options) -> w."""
 
-    def __init__(self, w, level=None, block_size=64 << 10, block_checksum=False, content_checksum=True, content_size=True):
+    def __init__(self, w, level=None, block_size=64 << 10, block_checksum=False, content_checksum=True, content_size=True,
+                 linked=False, dictionary=None, dict_id=None):
         self.w = w
         self._buf = bytearray()
-        self._opts = dict(level=level, block_size=block_size, block_checksum=block_checksum, content_checksum=content_checksum, content_size=content_size)
+        self._opts = dict(level=level, block_size=block_size, block_checksum=block_checksum, content_checksum=content_checksum, content_size=content_size,
+                          linked=linked, dictionary=dictionary, dict_id=dict_id)
+        if (linked or dictionary) and level is None:
+            raise ValueError("linked blocks and dictionaries need the high-compression encoder: choose a level from 1 to 12")
 
     def write(self, buf):
         self._buf += buf
