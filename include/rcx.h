@@ -64,6 +64,8 @@ enum rcx_status {
     RCX_E_ZLIB_DICT = 22,       /* "unsupported initial dictionary in the output stream" */
     RCX_E_ZLIB_HEADER_CHECKSUM = 23, /* "invalid zlib header checksum" */
     RCX_E_ZLIB_CHECKSUM = 24,   /* "invalid checksum on zlib stream" */
+    /* rcx_zlib_decode_dict_batch (extension): the stream's DICTID is not the caller's dict_id[i] */
+    RCX_E_ZLIB_DICT_ID = 25,    /* "zlib dictionary id mismatch" */
     /* rle.rs:153 */
     RCX_E_RLE_LONG_RUN = 30,    /* "Overly long run" */
     /* lz4.rs:366,376: InvalidInput with empty message */
@@ -253,6 +255,41 @@ int rcx_deflate_encode_level_batch(rcx_ctx*, const rcx_batch*, int level);
 int rcx_zlib_encode_level_batch(rcx_ctx*, const rcx_batch*, int level);
 int rcx_gzip_encode_level_batch(rcx_ctx*, const rcx_batch*, int level);
 uint64_t rcx_deflate_level_scratch_bytes(uint32_t nblocks, uint64_t max_block);
+/* DEFLATE and zlib at levels 2..9 with HISTORY (extension): zlib's preset dictionary (deflateSetDictionary, Python's zdict=), and
+ * chunks of one stream each primed with the 32 KiB before it.  hist_len is a host array of nblocks entries, or NULL (= all 0).  Block
+ * i is encoded exactly as rcx_deflate_encode_level_batch encodes it at that level (depths, parses, block-type choice, statuses,
+ * determinism, in_used, rcx_deflate_compression_bound), and its matches may also reach into the hist_len[i] (at most 32768, at most
+ * in_off[i]) bytes that lie directly before in_base + in_off[i].  The caller put them there; they are read and never written, and
+ * they may be another block's input.  ALL 32768 history bytes are within reach (DEFLATE's largest distance is 32768; LZ4's "65536
+ * counts as 65535" does not apply).  hist_len[i] > in_off[i] or > 32768 returns RCX_RC_BAD_ARG and rcx_last_error names the block.
+ * No emitted distance exceeds position + hist_len[i] or 32768; no byte in front of the history influences the output.  With hist_len
+ * NULL or all 0 every result is rcx_deflate_encode_level_batch's at that level, byte for byte.
+ * A level outside 2..9 returns RCX_RC_BAD_ARG: LEVEL 1 HAS NO HISTORY (its encoder has a hash finder of its own in LDS; as the
+ * greedy LZ4 encoder has none).  gzip has no dictionary and no variant.
+ * rcx_zlib_encode_dict_batch: where hist_len[i] > 0 the stream carries FDICT -- CMF/FLG with bit 5 set (FLEVEL as at that level,
+ * FCHECK recomputed), dict_id[i] big-endian, the DEFLATE data, the Adler-32 of the BLOCK alone -- and the slot needs the raw bound
+ * + 10; where hist_len[i] == 0 the stream is rcx_zlib_encode_level_batch's, byte for byte.  dict_id is the caller's: the Adler-32 of
+ * whatever dictionary the decoder will be handed, which may be longer than the 32 KiB that count; the library does not compute it.
+ * COST: the hash chains of a history are REBUILT for every block that names it, by one more workgroup per block, and take one more
+ * 64 KiB segment of 16-bit links (128 KiB) per block with history: rcx_deflate_hist_scratch_bytes counts every block with one.  For
+ * 64 KiB chunks linked by 32 KiB that is half as much chain work again, for a 2 KiB record behind a 32 KiB dictionary 17 times the
+ * record's.  A dictionary's table built once and shared, and history that is not contiguous with the block, are not provided.
+ * Rates on an MI355X: not measured (benchmarks/deflate_hist_rate.py measures them). */
+int rcx_deflate_encode_hist_batch(rcx_ctx*, const rcx_batch*, int level, const uint64_t* hist_len);
+int rcx_zlib_encode_dict_batch(rcx_ctx*, const rcx_batch*, int level, const uint64_t* hist_len, const uint32_t* dict_id);
+uint64_t rcx_deflate_hist_scratch_bytes(uint32_t nblocks, uint64_t max_block);
+/* Inflate with HISTORY (extension; the mirror of dict_len in rcx_lz4_decode_linked_batch).  Stream i decodes into its slot, and its
+ * matches may reach into the hist_len[i] (at most 32768, at most out_off[i]; anything else RCX_RC_BAD_ARG naming the block) bytes
+ * that lie directly before out_base + out_off[i].  The caller put them there; they are read and never written.  A distance beyond
+ * output so far + hist_len[i], or beyond 32768, is RCX_E_INVALID_HUFFMAN_CODE (flate.rs:314 with the history counted in).  Every
+ * other status, in_used, flags and out_len (the block's own bytes) is rcx_inflate_batch's; with hist_len NULL or all 0 so are all
+ * results.  One lane per stream (the kernel of rcx_inflate_batch's exact path); the wave-per-stream kernel takes no history.
+ * rcx_zlib_decode_dict_batch: FDICT set and hist_len[i] > 0 -- four DICTID bytes follow the header, count in in_used and must equal
+ * dict_id[i] (big-endian), else RCX_E_ZLIB_DICT_ID with out_len 0; FDICT set and hist_len[i] == 0 -- RCX_E_ZLIB_DICT, as
+ * rcx_zlib_decode_batch; FDICT clear -- the history is ignored (libz never asks for one) and the result is rcx_zlib_decode_batch's.
+ * The Adler-32 trailer covers the decoded block only. */
+int rcx_inflate_hist_batch(rcx_ctx*, const rcx_batch*, uint32_t* flags, const uint64_t* hist_len);
+int rcx_zlib_decode_dict_batch(rcx_ctx*, const rcx_batch*, uint32_t* flags, const uint64_t* hist_len, const uint32_t* dict_id);
 
 /* ---- BWT / MTF / DC --------------------------------------------------------- */
 /* reference: src/bwt/mod.rs:136-219 compute_suffixes + TransformIterator.
@@ -362,7 +399,8 @@ enum rcx_codec {
 };
 /* Ids of the batch entry points that rcx_launch_dev, rcx_multi_* and rcx_scratch_bytes do not take (enum rcx_codec stays as it is for
  * those): they name the entry point to rcx_ctx_set_variant / rcx_ctx_set_param, neither of which has a setting for them yet. */
-enum rcx_xcodec { RCX_XXH32 = 32, RCX_LZ4_DECODE_LINKED = 33, RCX_LZ4_ENCODE_HIST = 34, RCX_XCODEC_END = 35 };
+enum rcx_xcodec { RCX_XXH32 = 32, RCX_LZ4_DECODE_LINKED = 33, RCX_LZ4_ENCODE_HIST = 34, RCX_DEFLATE_ENCODE_HIST = 35, RCX_ZLIB_ENCODE_DICT = 36,
+                  RCX_INFLATE_HIST = 37, RCX_ZLIB_DECODE_DICT = 38, RCX_XCODEC_END = 39 };
 /* scratch bytes (HBM) the codec needs for nblocks blocks of <= max_block bytes.  Required for LZ4 encode, BWT and gzip
  * decode and the DEFLATE / zlib / gzip encoders; for RCX_INFLATE / RCX_ZLIB_DECODE it is what the default (wave-per-stream) decoder needs -- without it
  * rcx_launch_dev falls back to the lane-per-stream kernel (same results, slower on small batches). */

@@ -64,6 +64,7 @@ pub const RCX_E_ZLIB_WINDOW: i32 = 21;
 pub const RCX_E_ZLIB_DICT: i32 = 22;
 pub const RCX_E_ZLIB_HEADER_CHECKSUM: i32 = 23;
 pub const RCX_E_ZLIB_CHECKSUM: i32 = 24;
+pub const RCX_E_ZLIB_DICT_ID: i32 = 25;
 pub const RCX_E_RLE_LONG_RUN: i32 = 30;
 pub const RCX_E_LZ4_MAGIC: i32 = 40;
 pub const RCX_E_LZ4_VERSION: i32 = 41;
@@ -120,7 +121,11 @@ pub const RCX_CODEC_COUNT: c_int = 29;
 pub const RCX_XXH32: c_int = 32;
 pub const RCX_LZ4_DECODE_LINKED: c_int = 33;
 pub const RCX_LZ4_ENCODE_HIST: c_int = 34;
-pub const RCX_XCODEC_END: c_int = 35;
+pub const RCX_DEFLATE_ENCODE_HIST: c_int = 35;
+pub const RCX_ZLIB_ENCODE_DICT: c_int = 36;
+pub const RCX_INFLATE_HIST: c_int = 37;
+pub const RCX_ZLIB_DECODE_DICT: c_int = 38;
+pub const RCX_XCODEC_END: c_int = 39;
 
 #[link(name = "rcx")]
 extern "C" {
@@ -159,6 +164,12 @@ extern "C" {
     pub fn rcx_zlib_encode_level_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int) -> c_int;
     pub fn rcx_gzip_encode_level_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int) -> c_int;
     pub fn rcx_deflate_level_scratch_bytes(nblocks: u32, max_block: u64) -> u64;
+    // ---- DEFLATE / zlib with history (extension): preset dictionaries and primed chunks, levels 2..9, and their decoders
+    pub fn rcx_deflate_encode_hist_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int, hist_len: *const u64) -> c_int;
+    pub fn rcx_zlib_encode_dict_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int, hist_len: *const u64, dict_id: *const u32) -> c_int;
+    pub fn rcx_deflate_hist_scratch_bytes(nblocks: u32, max_block: u64) -> u64;
+    pub fn rcx_inflate_hist_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32, hist_len: *const u64) -> c_int;
+    pub fn rcx_zlib_decode_dict_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32, hist_len: *const u64, dict_id: *const u32) -> c_int;
     // ---- BWT / MTF / DC (src/bwt/mod.rs, mtf.rs, dc.rs)
     pub fn rcx_bwt_forward_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;
     pub fn rcx_bwt_suffixes_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;

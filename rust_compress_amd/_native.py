@@ -47,6 +47,8 @@ EXPORTS = [
     "rcx_deflate_encode_level_batch", "rcx_zlib_encode_level_batch", "rcx_gzip_encode_level_batch", "rcx_deflate_level_scratch_bytes",
     "rcx_xxh32_batch", "rcx_lz4_decode_linked_batch",
     "rcx_lz4_encode_hc_hist_batch", "rcx_lz4_hc_hist_scratch_bytes",
+    "rcx_deflate_encode_hist_batch", "rcx_zlib_encode_dict_batch", "rcx_deflate_hist_scratch_bytes",
+    "rcx_inflate_hist_batch", "rcx_zlib_decode_dict_batch",
 ]
 
 
@@ -118,6 +120,12 @@ def lib():
         L.rcx_lz4_encode_hc_hist_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p]
         L.rcx_lz4_hc_hist_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64]
         L.rcx_lz4_hc_hist_scratch_bytes.restype = C.c_uint64
+        L.rcx_deflate_encode_hist_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p]
+        L.rcx_zlib_encode_dict_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p]
+        L.rcx_inflate_hist_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p]
+        L.rcx_zlib_decode_dict_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rcx_deflate_hist_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64]
+        L.rcx_deflate_hist_scratch_bytes.restype = C.c_uint64
         L.rcx_deflate_level_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64]
         L.rcx_deflate_level_scratch_bytes.restype = C.c_uint64
         for name in ("rcx_inflate_batch", "rcx_zlib_decode_batch", "rcx_adler32_batch", "rcx_crc32_batch",

@@ -13,6 +13,32 @@ def deflate_bound(n):
     return int(N.lib().rcx_deflate_compression_bound(n))
 
 
+def _per_blob(zdict, n):
+    """one dictionary for all blobs, or a list with one entry per blob"""
+    if isinstance(zdict, (bytes, bytearray, memoryview)):
+        return [bytes(zdict)] * n
+    if len(zdict) != n:
+        raise ValueError("zdict: bytes, or one entry (bytes or None) per blob")
+    return [bytes(d) if d else b"" for d in zdict]
+
+
+def _adler32(d):
+    import zlib
+    return zlib.adler32(d) if d else 0
+
+
+def _pack_hist(blobs, histories, limit):
+    """the input buffer history, block, history, block, ...: -> (uint8 array, in_off, hist_len); a history's last `limit` bytes count"""
+    buf, off, hl = bytearray(), [], []
+    for blob, h in zip(blobs, histories):
+        h = bytes(h)[-limit:] if h else b""
+        buf += h
+        off.append(len(buf))
+        hl.append(len(h))
+        buf += bytes(blob)
+    return np.frombuffer(bytes(buf) + b"\0" * 16, np.uint8), off, hl
+
+
 class RcxError(RuntimeError):
     pass
 
@@ -157,8 +183,49 @@ class Context:
     def inflate(self, blobs, caps):
         return self._run_host("rcx_inflate_batch", blobs, caps, extra_out=True)
 
-    def zlib_decode(self, blobs, caps):
-        return self._run_host("rcx_zlib_decode_batch", blobs, caps, extra_out=True)
+    def zlib_decode(self, blobs, caps, zdict=None):
+        """One zlib stream per blob.  zdict (bytes for all blobs, or a list with one entry, bytes or None, per blob): the preset
+        dictionary of streams that carry FDICT (rcx_zlib_decode_dict_batch): its last 32 KiB are placed in front of every slot and its
+        Adler-32 must be the stream's DICTID.  None: rcx_zlib_decode_batch, which refuses FDICT."""
+        if zdict is None:
+            return self._run_host("rcx_zlib_decode_batch", blobs, caps, extra_out=True)
+        dicts = _per_blob(zdict, len(blobs))
+        return self._inflate_hist(blobs, dicts, caps, [_adler32(d) for d in dicts])
+
+    def inflate_hist_blocks(self, blobs, histories, caps):
+        """One raw DEFLATE stream per blob, decoded with HISTORY (rcx_inflate_hist_batch): histories[i] (bytes or None; its last
+        32 KiB count) is put directly in front of blob i's slot in the output buffer and the stream's matches may reach into it."""
+        if len(histories) != len(blobs):
+            raise ValueError("histories: one entry (bytes or None) per blob")
+        return self._inflate_hist(blobs, histories, caps, None)
+
+    def _inflate_hist(self, blobs, histories, caps, dict_id):
+        n = len(blobs)
+        base, off, lens = B.pack(blobs)
+        hists = [bytes(h)[-32768:] if h else b"" for h in histories]
+        ooff, at = np.zeros(max(n, 1), np.uint64), 0
+        for i in range(n):                                       # history, slot (16-byte aligned, as B.layout's), history, slot, ...
+            at = (at + len(hists[i]) + 15) & ~15
+            ooff[i] = at
+            at += int(caps[i])
+        out = np.zeros(at + 16, dtype=np.uint8)
+        for i, h in enumerate(hists):
+            if h:
+                out[int(ooff[i]) - len(h):int(ooff[i])] = np.frombuffer(h, np.uint8)
+        ocap = np.array(list(caps) or [0], np.uint64)
+        hl = np.array([len(h) for h in hists] or [0], np.uint64)
+        out_len = np.zeros(max(n, 1), np.uint64)
+        in_used = np.zeros(max(n, 1), np.uint64)
+        status = np.zeros(max(n, 1), np.int32)
+        flags = np.zeros(max(n, 1), np.uint32)
+        p = lambda a: a.ctypes.data
+        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
+        if dict_id is None:
+            self._chk(N.lib().rcx_inflate_hist_batch(self._h, C.byref(b), C.c_void_p(p(flags)), C.c_void_p(p(hl))))
+        else:
+            ids = np.array(list(dict_id) or [0], np.uint32)
+            self._chk(N.lib().rcx_zlib_decode_dict_batch(self._h, C.byref(b), C.c_void_p(p(flags)), C.c_void_p(p(hl)), C.c_void_p(p(ids))))
+        return Result(B.unpack(out, ooff[:n], out_len[:n]), out_len[:n], in_used[:n], status[:n], flags[:n])
 
     def adler32(self, blobs):
         return self._run_host("rcx_adler32_batch", blobs, None, extra_out=True, needs_out=False)
@@ -182,9 +249,57 @@ class Context:
         rcx_deflate_compression_bound.  level 1..9 (rcx_deflate_encode_level_batch; 1 is the default encoder's bytes)."""
         return self._deflate_encode("rcx_deflate_encode", blobs, caps, 0, level)
 
-    def zlib_encode(self, blobs, caps=None, level=1):
-        """One zlib stream (RFC 1950: 78 01 at level 1, DEFLATE, Adler-32) per blob; caps default to the DEFLATE bound + 6."""
-        return self._deflate_encode("rcx_zlib_encode", blobs, caps, 6, level)
+    def zlib_encode(self, blobs, caps=None, level=1, zdict=None):
+        """One zlib stream (RFC 1950: 78 01 at level 1, DEFLATE, Adler-32) per blob; caps default to the DEFLATE bound + 6.
+        zdict (bytes for all blobs, or a list with one entry, bytes or None, per blob; levels 2..9): a preset dictionary as Python's
+        zlib takes it (rcx_zlib_encode_dict_batch) -- its last 32 KiB are placed in front of every block, the stream carries FDICT and
+        DICTID = zlib.adler32(zdict), and caps default to the bound + 10."""
+        if zdict is None:
+            return self._deflate_encode("rcx_zlib_encode", blobs, caps, 6, level)
+        dicts = _per_blob(zdict, len(blobs))
+        base, off, hl = _pack_hist(blobs, dicts, 32768)
+        return self._deflate_hist(base, off, [len(b) for b in blobs], hl, level, caps, [_adler32(d) for d in dicts])
+
+    def deflate_encode_hist(self, base, in_off, in_len, hist_len, level=6, caps=None):
+        """rcx_deflate_encode_hist_batch (levels 2..9) over a buffer the caller laid out: block i is base[in_off[i] : in_off[i] +
+        in_len[i]] (base: a numpy uint8 array) and its matches may reach into the hist_len[i] (at most 32768) bytes below in_off[i]
+        -- a dictionary put there, or the bytes before a chunk of one long input.  hist_len None: no history."""
+        return self._deflate_hist(base, in_off, in_len, hist_len, level, caps, None)
+
+    def deflate_encode_hist_blocks(self, blobs, histories, level=6, caps=None):
+        """One raw DEFLATE stream per blob (levels 2..9), with HISTORY: histories[i] (bytes or None; its last 32 KiB count) is put
+        directly in front of blobs[i] in the input buffer and the block's matches may reach into it.  The stream decodes behind the
+        same bytes (inflate_hist_blocks, or zlib.decompressobj(-15, zdict=...))."""
+        if len(histories) != len(blobs):
+            raise ValueError("histories: one entry (bytes or None) per blob")
+        base, off, hl = _pack_hist(blobs, histories, 32768)
+        return self.deflate_encode_hist(base, off, [len(b) for b in blobs], hl, level, caps)
+
+    def _deflate_hist(self, base, in_off, in_len, hist_len, level, caps, dict_id):
+        n = len(in_off)
+        off = np.ascontiguousarray(in_off, np.uint64) if n else np.zeros(1, np.uint64)
+        lens = np.ascontiguousarray(in_len, np.uint64) if n else np.zeros(1, np.uint64)
+        if caps is None:
+            caps = [deflate_bound(int(l)) + (10 if dict_id is not None else 0) for l in lens[:n]]
+        total, ooff, ocap = B.layout(caps)
+        out = np.zeros(total, dtype=np.uint8)
+        out_len = np.zeros(max(n, 1), np.uint64)
+        in_used = np.zeros(max(n, 1), np.uint64)
+        status = np.zeros(max(n, 1), np.int32)
+        hist = np.ascontiguousarray(hist_len, np.uint64) if hist_len is not None else None
+        if hist is not None and hist.size != n:
+            raise ValueError("hist_len: one entry per block")
+        if base.size == 0:
+            base = np.zeros(1, np.uint8)
+        p = lambda a: a.ctypes.data
+        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
+        hp = C.c_void_p(p(hist) if hist is not None and n else None)
+        if dict_id is None:
+            self._chk(N.lib().rcx_deflate_encode_hist_batch(self._h, C.byref(b), int(level), hp))
+        else:
+            ids = np.array(list(dict_id) or [0], np.uint32)
+            self._chk(N.lib().rcx_zlib_encode_dict_batch(self._h, C.byref(b), int(level), hp, C.c_void_p(p(ids))))
+        return Result(B.unpack(out, ooff, out_len[:n]), out_len[:n], in_used[:n], status[:n], None)
 
     def gzip_encode(self, blobs, caps=None, level=1):
         """One gzip member (RFC 1952, no optional header fields, MTIME 0, OS 255) per blob; caps default to the DEFLATE bound + 18."""

@@ -49,7 +49,14 @@
 #define DE_BIGW 16448u                 /* LDS words: the hash table, then the packed block (<= 8 * DE_SEG + 84 bits + slack) */
 #define DE_STG_BYTES (DE_SEG + 256u)   /* a segment's packed bits in scratch */
 
-enum { DE_RAW = 0, DE_ZLIB = 1, DE_GZIP = 2 };
+enum { DE_RAW = 0, DE_ZLIB = 1, DE_GZIP = 2,
+       DE_ZDICT = 3 };   // zlib whose stream b carries FDICT and four DICTID bytes when a.aux[b] != 0 (k_deflate_hc_hist.hip fills them in)
+// the bytes in front of stream b's DEFLATE data and behind it
+template <int FMT> __device__ __forceinline__ uint32_t de_hdr(const rcx_kargs& a, uint32_t b)
+{
+    return FMT == DE_ZDICT ? (a.aux[b] ? 6u : 2u) : FMT == DE_ZLIB ? 2u : FMT == DE_GZIP ? 10u : 0u;
+}
+template <int FMT> __device__ __forceinline__ uint32_t de_trl() { return FMT == DE_ZLIB || FMT == DE_ZDICT ? 4u : FMT == DE_GZIP ? 8u : 0u; }
 static constexpr uint8_t DE_ORD[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};   // code-length code order
 
 struct DeScratch {
@@ -530,7 +537,8 @@ __global__ __launch_bounds__(256) void k_de_scan(rcx_kargs a, DeScratch d)
     const uint32_t lane = rcx_lane();
     const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     if (b >= a.nblocks) return;
-    const uint32_t HDR = FMT == DE_ZLIB ? 2 : FMT == DE_GZIP ? 10 : 0, TRL = FMT == DE_ZLIB ? 4 : FMT == DE_GZIP ? 8 : 0;
+    const uint32_t HDR = de_hdr<FMT>(a, b), TRL = de_trl<FMT>();
+    constexpr bool ZL = FMT == DE_ZLIB || FMT == DE_ZDICT;
     const uint64_t len = a.in_len[b];
     const uint32_t f0 = d.seg_first[b], f1 = d.seg_first[b + 1];
     int st = RCX_OK;
@@ -538,7 +546,7 @@ __global__ __launch_bounds__(256) void k_de_scan(rcx_kargs a, DeScratch d)
     else if (f1 > d.cap) st = RCX_E_MALFORMED;                             // scratch smaller than rcx_scratch_bytes asked for
     uint64_t off = 0;
     if (!st && len == 0) off = 10;                                         // a lone final fixed block: 1, 01, end-of-block
-    uint32_t ck = FMT == DE_ZLIB ? 1u : 0u;                                // the checksum of nothing; then segment by segment
+    uint32_t ck = ZL ? 1u : 0u;                                            // the checksum of nothing; then segment by segment
     const uint32_t K64 = FMT == DE_GZIP && !st && f1 - f0 > 1 ? RCX_UNI(rcx_crc_xpow(8ull * DE_SEG)) : 0u;
     if (!st) {
         for (uint32_t c0 = f0; c0 < f1; c0 += 64) {
@@ -595,7 +603,7 @@ __global__ __launch_bounds__(256) void k_de_scan(rcx_kargs a, DeScratch d)
         if (a.in_used) a.in_used[b] = st ? 0 : len;
         if (!st) {
             uint8_t* o = a.out_base + a.out_off[b];
-            if (FMT == DE_ZLIB) { o[0] = 0x78; o[1] = 0x01; }               // deflate, 32 KiB window, fastest; (0x7801 % 31 == 0)
+            if (ZL) { o[0] = 0x78; o[1] = 0x01; }                           // deflate, 32 KiB window, fastest; (0x7801 % 31 == 0)
             if (FMT == DE_GZIP) {
                 o[0] = 0x1f; o[1] = 0x8b; o[2] = 8;
                 for (int i = 3; i < 9; i++) o[i] = 0;                       // FLG, MTIME, XFL
@@ -603,7 +611,7 @@ __global__ __launch_bounds__(256) void k_de_scan(rcx_kargs a, DeScratch d)
             }
             if (len == 0) { o[HDR] = 0x03; o[HDR + 1] = 0x00; }
             uint8_t* t = o + HDR + dbytes;
-            if (FMT == DE_ZLIB) { t[0] = (uint8_t)(ck >> 24); t[1] = (uint8_t)(ck >> 16); t[2] = (uint8_t)(ck >> 8); t[3] = (uint8_t)ck; }
+            if (ZL) { t[0] = (uint8_t)(ck >> 24); t[1] = (uint8_t)(ck >> 16); t[2] = (uint8_t)(ck >> 8); t[3] = (uint8_t)ck; }
             if (FMT == DE_GZIP) {
                 const uint32_t isz = (uint32_t)len;
                 for (int i = 0; i < 4; i++) { t[i] = (uint8_t)(ck >> (8 * i)); t[4 + i] = (uint8_t)(isz >> (8 * i)); }
@@ -667,7 +675,6 @@ template <int FMT>
 __global__ __launch_bounds__(256) void k_de_place(rcx_kargs a, DeScratch d)
 {
     const uint32_t lim = de_lim(a, d);
-    const uint32_t HDR = FMT == DE_ZLIB ? 2 : FMT == DE_GZIP ? 10 : 0;
     for (uint32_t g = blockIdx.x; g < lim; g += gridDim.x) {
         const LzcSeg s = de_seg(a, d, g);
         const uint32_t b = s.b;
@@ -677,7 +684,8 @@ __global__ __launch_bounds__(256) void k_de_place(rcx_kargs a, DeScratch d)
         const uint64_t len = s.len;                                        // (a stream that has segments is shorter than 2^32)
         const bool last = g + 1 == f1;
         const uint64_t o0 = d.seg_off[g], o1 = o0 + d.seg_bits[g];
-        const uint64_t dbytes = a.out_len[b] - HDR - (FMT == DE_ZLIB ? 4 : FMT == DE_GZIP ? 8 : 0);
+        const uint32_t HDR = de_hdr<FMT>(a, b);
+        const uint64_t dbytes = a.out_len[b] - HDR - de_trl<FMT>();
         uint8_t* o = a.out_base + a.out_off[b] + HDR;
         const uint64_t t0 = (o0 + 31) / 32, t1 = (o1 + 31) / 32;          // the words whose first bit lies in [o0, o1)
         for (uint64_t t = t0 + threadIdx.x; t < t1; t += blockDim.x) {

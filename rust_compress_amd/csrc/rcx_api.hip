@@ -129,6 +129,7 @@ extern "C" const char* rcx_status_string(int s)
     case RCX_E_ZLIB_FORMAT: return "unsupported zlib stream format";
     case RCX_E_ZLIB_WINDOW: return "unsupported zlib window size";
     case RCX_E_ZLIB_DICT: return "unsupported initial dictionary in the output stream";
+    case RCX_E_ZLIB_DICT_ID: return "zlib dictionary id mismatch";
     case RCX_E_ZLIB_HEADER_CHECKSUM: return "invalid zlib header checksum";
     case RCX_E_ZLIB_CHECKSUM: return "invalid checksum on zlib stream";
     case RCX_E_RLE_LONG_RUN: return "Overly long run";
@@ -164,6 +165,11 @@ extern "C" uint64_t rcx_lz4_hc_hist_scratch_bytes(uint32_t nblocks, uint64_t max
 {
     return rcx_tu_lz4_hc_hist_scratch(nblocks, (uint64_t)nblocks * rcx_tu_lz4_hc_segments(max_block), nblocks);
 }
+// (every block counted with a history: one more segment of links each)
+extern "C" uint64_t rcx_deflate_hist_scratch_bytes(uint32_t nblocks, uint64_t max_block)
+{
+    return rcx_tu_deflate_hist_scratch(nblocks, (uint64_t)nblocks * rcx_tu_deflate_encode_segments(max_block), nblocks);
+}
 
 // ---- scratch requirements ---------------------------------------------------------------------
 extern "C" uint64_t rcx_scratch_bytes(int codec, uint32_t nblocks, uint64_t max_block)
@@ -196,7 +202,8 @@ struct rcx_call {
     bool needs_out;
     uint32_t seed;                       // XXH32
     const link_tables* link;             // linked LZ4 decode, else null
-    uint32_t nhist;                      // LZ4 HC encode with history: the blocks that have one (their lengths are aux_in)
+    uint32_t nhist;                      // LZ4 HC / DEFLATE encode with history: the blocks that have one (their lengths are aux_in)
+    uint32_t aux_words;                  // words per block of aux_in: 1, or 2 (the zlib calls with history: lengths, then DICTIDs)
 };
 
 // ---- per-codec traits of the host path ------------------------------------------------------------------------------------------------
@@ -205,6 +212,7 @@ enum scratch_rule { SCRATCH_BY_CODEC,                                  // rcx_sc
                     SCRATCH_DEFLATE_SEGS, SCRATCH_DEFLATE_LEVEL_SEGS,  // the staging of the real segments (+ chains, parse: levels 2..9)
                     SCRATCH_HC_SEGS,                                   // HC: the chains and parse of the real segments
                     SCRATCH_HC_HIST_SEGS,                              // ... and the chains of the real histories
+                    SCRATCH_DEFLATE_HIST_SEGS,                         // DEFLATE levels 2..9: the real segments and the real histories
                     SCRATCH_DC_OPTIONAL };                             // chunk states: none with contexts, and none when they cannot be had
 enum back_policy { BACK_USED_SPAN, BACK_INFLATE /* mirrored: the streams the first pass handed back */, BACK_CHAINS };
 struct codec_traits {
@@ -231,6 +239,9 @@ static codec_traits traits_of(int codec, uint32_t param)
     // (and so does the LZ4 HC encoder: a block's slot holds its bound, more than the block takes)
     case RCX_LZ4_ENCODE: if (param) { t.preload_out = true; t.scratch = SCRATCH_HC_SEGS; } break;
     case RCX_LZ4_ENCODE_HIST: t.preload_out = true; t.scratch = SCRATCH_HC_HIST_SEGS; break;
+    case RCX_DEFLATE_ENCODE_HIST: case RCX_ZLIB_ENCODE_DICT: t.preload_out = true; t.scratch = SCRATCH_DEFLATE_HIST_SEGS; break;
+    // the decoders with history read the bytes the caller put in front of the slots: the staged output span starts as the caller's
+    case RCX_INFLATE_HIST: case RCX_ZLIB_DECODE_DICT: t.preload_out = true; break;
     case RCX_DC_ENCODE: t.scratch = SCRATCH_DC_OPTIONAL; break;
     case RCX_LZ4_DECODE_LINKED: t.back = BACK_CHAINS; break;
     case RCX_ADLER32: case RCX_CRC32: case RCX_XXH32: t.needs_out = false; break;
@@ -240,7 +251,7 @@ static codec_traits traits_of(int codec, uint32_t param)
 }
 static rcx_call call_of(int codec, uint32_t param = 0, const uint32_t* aux_in = nullptr, uint32_t* aux_out = nullptr, const uint64_t* n_out = nullptr)
 {
-    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr, 0};
+    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr, 0, 1};
 }
 
 // ---- kernel arguments: built here and nowhere else ---------------------------------------------------------------------------------------
@@ -311,6 +322,14 @@ static int launch_codec(rcx_ctx* c, const rcx_call& call, rcx_kargs& k)
     case RCX_ZLIB_DECODE:
         rcx_tu_inflate(s, k, codec == RCX_ZLIB_DECODE, v);
         break;
+    case RCX_INFLATE_HIST: case RCX_ZLIB_DECODE_DICT:            // k.aux: the history lengths (then the DICTIDs), never null
+        if (!k.aux) { c->err = "inflate with history: use rcx_inflate_hist_batch / rcx_zlib_decode_dict_batch"; return RCX_RC_BAD_ARG; }
+        rcx_tu_inflate_hist(s, k, codec == RCX_ZLIB_DECODE_DICT);
+        break;
+    case RCX_DEFLATE_ENCODE_HIST: case RCX_ZLIB_ENCODE_DICT: {   // the codec parameter: the level, 2..9; k.aux: the history lengths (then the DICTIDs)
+        int rc = rcx_tu_deflate_encode_hist(s, k, codec == RCX_ZLIB_ENCODE_DICT ? 1 : 0, (int)call.param, call.nhist, c->err);
+        if (rc) return rc;
+        break; }
     case RCX_ADLER32:
         rcx_tu_adler32(s, k);
         break;
@@ -485,7 +504,8 @@ static int pack_descriptors(rcx_ctx* c, const rcx_call& call, batch_state& st)
 {
     const rcx_batch* b = st.b;
     const size_t N = st.n;
-    const size_t desc_bytes = (5 * N + 2 * N) * 8 + 2 * N * 4 + 64;
+    const size_t AW = call.aux_in ? call.aux_words : 1;                                          // aux words per block (in; one comes back)
+    const size_t desc_bytes = (5 * N + 2 * N) * 8 + (1 + AW) * N * 4 + 64;
     HIPCHK(c, c->d_desc.reserve(desc_bytes));
     if (desc_bytes > c->h_desc_cap) {
         if (c->h_desc) (void)hipHostFree(c->h_desc);
@@ -502,9 +522,9 @@ static int pack_descriptors(rcx_ctx* c, const rcx_call& call, batch_state& st)
     st.h_status = (int32_t*)(h64 + 7 * N);
     st.h_aux = (uint32_t*)(st.h_status + N);
     for (size_t i = 0; i < N; i++) st.h_status[i] = RCX_E_MALFORMED;
-    if (call.aux_in) memcpy(st.h_aux, call.aux_in, N * 4); else memset(st.h_aux, 0, N * 4);
+    if (call.aux_in) memcpy(st.h_aux, call.aux_in, AW * N * 4); else memset(st.h_aux, 0, N * 4);
     memset(h64 + 5 * N, 0, 2 * N * 8);
-    HIPCHK(c, hipMemcpyAsync(c->d_desc.p, c->h_desc, (7 * N) * 8 + 2 * N * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_desc.p, c->h_desc, (7 * N) * 8 + (1 + AW) * N * 4, hipMemcpyHostToDevice, c->stream));
     uint64_t* d64 = (uint64_t*)c->d_desc.p;
     int32_t* d_status = (int32_t*)(d64 + 7 * N);
     st.dv = {st.d_in, d64, d64 + N, st.d_out, d64 + 2 * N, d64 + 3 * N, d64 + 5 * N, d64 + 6 * N, d_status, (uint32_t*)(d_status + N), st.n};
@@ -531,6 +551,10 @@ static int reserve_scratch(rcx_ctx* c, const rcx_call& call, batch_state& st)
     case SCRATCH_HC_HIST_SEGS:
         for (uint32_t i = 0; i < n; i++) segs += rcx_tu_lz4_hc_segments(b->in_len[i]);
         sb = rcx_tu_lz4_hc_hist_scratch(n, segs, call.nhist);
+        break;
+    case SCRATCH_DEFLATE_HIST_SEGS:
+        for (uint32_t i = 0; i < n; i++) segs += rcx_tu_deflate_encode_segments(b->in_len[i]);
+        sb = rcx_tu_deflate_hist_scratch(n, segs, call.nhist);
         break;
     case SCRATCH_DC_OPTIONAL:                                       // withctx: the wave-per-block kernel encodes, no chunk states
         sb = call.param ? 0 : rcx_scratch_bytes(call.codec, n, st.sp.max_block);
@@ -806,6 +830,51 @@ static int deflate_level_batch(rcx_ctx* c, int codec, const rcx_batch* b, int le
 extern "C" int rcx_deflate_encode_level_batch(rcx_ctx* c, const rcx_batch* b, int level) { return deflate_level_batch(c, RCX_DEFLATE_ENCODE, b, level); }
 extern "C" int rcx_zlib_encode_level_batch(rcx_ctx* c, const rcx_batch* b, int level) { return deflate_level_batch(c, RCX_ZLIB_ENCODE, b, level); }
 extern "C" int rcx_gzip_encode_level_batch(rcx_ctx* c, const rcx_batch* b, int level) { return deflate_level_batch(c, RCX_GZIP_ENCODE, b, level); }
+// DEFLATE / zlib at levels 2..9 with history.  The history travels in with the input (rcx_plan_spans stages [0, in_span), and a history
+// lies below its block); lengths and DICTIDs go to the kernels as 32-bit words in the descriptors' aux array (rcx_plan_hist).
+static int deflate_hist_batch(rcx_ctx* c, int codec, const rcx_batch* b, int level, const uint64_t* hist_len, const uint32_t* dict_id)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    if (level < 2 || level > 9) { c->err = "deflate encode with history: level must be 2..9 (level 1 has none)"; return RCX_RC_BAD_ARG; }
+    rcx_call call = call_of(codec, (uint32_t)level);
+    if (!hist_len || !b || !b->nblocks) return run_batch(c, call, b);
+    if (!b->in_off) { c->err = "null descriptor array"; return RCX_RC_BAD_ARG; }
+    if (codec == RCX_ZLIB_ENCODE_DICT && !dict_id) { c->err = "zlib encode with dictionary: null dict_id array"; return RCX_RC_BAD_ARG; }
+    std::vector<uint32_t> aux;
+    if (!rcx_plan_hist(b->nblocks, hist_len, b->in_off, 32768, dict_id, "deflate encode", aux, call.nhist, c->err)) return RCX_RC_BAD_ARG;
+    call.aux_in = aux.data(); call.aux_words = dict_id ? 2 : 1;
+    return run_batch(c, call, b);                                // (waits for the stream: the words above may go)
+}
+extern "C" int rcx_deflate_encode_hist_batch(rcx_ctx* c, const rcx_batch* b, int level, const uint64_t* hist_len)
+{
+    return deflate_hist_batch(c, RCX_DEFLATE_ENCODE_HIST, b, level, hist_len, nullptr);
+}
+extern "C" int rcx_zlib_encode_dict_batch(rcx_ctx* c, const rcx_batch* b, int level, const uint64_t* hist_len, const uint32_t* dict_id)
+{
+    return deflate_hist_batch(c, RCX_ZLIB_ENCODE_DICT, b, level, hist_len, dict_id);
+}
+// Inflate with history: the history lies in front of the slot in the OUTPUT buffer and is staged with it (preload_out).  Without
+// lengths the call is the plain one.
+static int inflate_hist_batch(rcx_ctx* c, int codec, const rcx_batch* b, uint32_t* flags, const uint64_t* hist_len, const uint32_t* dict_id)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    if (!hist_len || !b || !b->nblocks) return run_batch(c, call_of(codec == RCX_ZLIB_DECODE_DICT ? RCX_ZLIB_DECODE : RCX_INFLATE, 0, nullptr, flags), b);
+    if (!b->out_off) { c->err = "null output descriptor"; return RCX_RC_BAD_ARG; }
+    if (codec == RCX_ZLIB_DECODE_DICT && !dict_id) { c->err = "zlib decode with dictionary: null dict_id array"; return RCX_RC_BAD_ARG; }
+    rcx_call call = call_of(codec, 0, nullptr, flags);
+    std::vector<uint32_t> aux;
+    if (!rcx_plan_hist(b->nblocks, hist_len, b->out_off, 32768, dict_id, "inflate", aux, call.nhist, c->err)) return RCX_RC_BAD_ARG;
+    call.aux_in = aux.data(); call.aux_words = dict_id ? 2 : 1;
+    return run_batch(c, call, b);
+}
+extern "C" int rcx_inflate_hist_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags, const uint64_t* hist_len)
+{
+    return inflate_hist_batch(c, RCX_INFLATE_HIST, b, flags, hist_len, nullptr);
+}
+extern "C" int rcx_zlib_decode_dict_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags, const uint64_t* hist_len, const uint32_t* dict_id)
+{
+    return inflate_hist_batch(c, RCX_ZLIB_DECODE_DICT, b, flags, hist_len, dict_id);
+}
 extern "C" int rcx_bwt_forward_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_FORWARD, 0, nullptr, origin), b); }
 extern "C" int rcx_bwt_suffixes_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_SUFFIXES, 0, nullptr, origin), b); }
 extern "C" int rcx_bwt_inversion_table_batch(rcx_ctx* c, const rcx_batch* b, const uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_INVERSION_TABLE, 0, origin), b); }

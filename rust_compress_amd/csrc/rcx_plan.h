@@ -132,6 +132,29 @@ inline bool rcx_plan_chains(uint32_t n, const uint8_t* link, const uint64_t* dic
     return true;
 }
 
+// ---- histories (the DEFLATE calls with history) ---------------------------------------------------------------------------------------
+// The kernels' aux words of n blocks with histories: aux[i] = hist_len[i], then (ids != null: the zlib forms) aux[n + i] = ids[i].
+// hist_len[i] bytes lie directly before off[i] (in_off for an encoder, out_off for a decoder) in the same buffer: at most max_hist and
+// at most off[i].  nhist: the blocks with a history.  false: `err` (prefixed with `what`) names the block.  n > 0, hist_len != null.
+inline bool rcx_plan_hist(uint32_t n, const uint64_t* hist_len, const uint64_t* off, uint64_t max_hist, const uint32_t* ids,
+                          const char* what, std::vector<uint32_t>& aux, uint32_t& nhist, std::string& err)
+{
+    aux.assign((ids ? 2 : 1) * (size_t)n, 0);
+    nhist = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (hist_len[i] > off[i] || hist_len[i] > max_hist) {
+            err = std::string(what) + ": block " + std::to_string(i) + ": a history of " + std::to_string(hist_len[i]) + " bytes "
+                + (hist_len[i] > max_hist ? "(at most " + std::to_string(max_hist) + ")"
+                                          : "does not fit in front of offset " + std::to_string(off[i]));
+            return false;
+        }
+        aux[i] = (uint32_t)hist_len[i];
+        nhist += hist_len[i] ? 1u : 0u;
+        if (ids) aux[(size_t)n + i] = ids[i];
+    }
+    return true;
+}
+
 // ---- what travels back ------------------------------------------------------------------------------------------------------------------
 // only what was produced: the span up to the last byte any block wrote, not the slots' capacity
 inline uint64_t rcx_plan_used_span(uint32_t n, const uint64_t* out_off, const uint64_t* out_cap, const uint64_t* out_len)

@@ -15,6 +15,8 @@ void rcx_tu_lz4_decode_mirror_again(hipStream_t s, rcx_kargs& k);
 uint64_t rcx_tu_lz4_encode_scratch(uint32_t nblocks);
 // tu_inflate.hip
 void rcx_tu_inflate(hipStream_t s, rcx_kargs& k, bool zlib, int variant);
+// ... with history (k_inflate_hist.hip): k.aux = n history lengths (uint32), then n DICTIDs (zlib); flags come back in the first n
+void rcx_tu_inflate_hist(hipStream_t s, rcx_kargs& k, bool zlib);
 void rcx_tu_adler32(hipStream_t s, rcx_kargs& k);
 void rcx_tu_crc32(hipStream_t s, rcx_kargs& k);
 void rcx_tu_gzip_decode(hipStream_t s, rcx_kargs& k, int variant);
@@ -38,6 +40,10 @@ uint64_t rcx_tu_deflate_encode_scratch(uint32_t nblocks, uint64_t nsegs);
 uint64_t rcx_tu_deflate_encode_segments(uint64_t len);
 int rcx_tu_deflate_encode_level(hipStream_t s, rcx_kargs& k, int fmt, int level, std::string& err);    // level 1..9 (1: as above)
 uint64_t rcx_tu_deflate_level_scratch(uint32_t nblocks, uint64_t nsegs);
+// ... levels 2..9 with history (k_deflate_hc_hist.hip), fmt 0 or 1: k.aux = n history lengths (uint32), then n DICTIDs (zlib), or null;
+// nhist = the blocks that have one
+int rcx_tu_deflate_encode_hist(hipStream_t s, rcx_kargs& k, int fmt, int level, uint32_t nhist, std::string& err);
+uint64_t rcx_tu_deflate_hist_scratch(uint32_t nblocks, uint64_t nsegs, uint64_t nhist);
 // tu_lz4_hc.hip (level 1..12)
 int rcx_tu_lz4_hc(hipStream_t s, rcx_kargs& k, int level, std::string& err);
 uint64_t rcx_tu_lz4_hc_scratch(uint32_t nblocks, uint64_t nsegs);
