@@ -199,7 +199,7 @@ int rcx_lz4_decode_linked_batch(rcx_ctx*, const rcx_batch*, const uint8_t* link,
  * COST: the hash chains of a history are REBUILT for every block that names it, by one more workgroup per block (one more 64 KiB
  * segment of 16-bit links per block with history: rcx_lz4_hc_hist_scratch_bytes counts every block with one) -- up to twice the chain
  * work for linked 64 KiB blocks, 17 times for a 2 KiB record behind a 32 KiB dictionary.  A dictionary's table built once and attached
- * to many blocks, and history that is not contiguous with the block, are not provided.  benchmarks/lz4_hist_rate.py
+ * to many blocks, and history that is not contiguous with the block: rcx_lz4_encode_hc_shared_batch.  benchmarks/lz4_hist_rate.py
  * measures the rebuild. */
 int rcx_lz4_encode_hc_hist_batch(rcx_ctx*, const rcx_batch*, int level, const uint64_t* hist_len);
 uint64_t rcx_lz4_hc_hist_scratch_bytes(uint32_t nblocks, uint64_t max_block);
@@ -273,11 +273,49 @@ uint64_t rcx_deflate_level_scratch_bytes(uint32_t nblocks, uint64_t max_block);
  * COST: the hash chains of a history are REBUILT for every block that names it, by one more workgroup per block, and take one more
  * 64 KiB segment of 16-bit links (128 KiB) per block with history: rcx_deflate_hist_scratch_bytes counts every block with one.  For
  * 64 KiB chunks linked by 32 KiB that is half as much chain work again, for a 2 KiB record behind a 32 KiB dictionary 17 times the
- * record's.  A dictionary's table built once and shared, and history that is not contiguous with the block, are not provided.
- * Rates on an MI355X: not measured (benchmarks/deflate_hist_rate.py measures them). */
+ * record's.  A dictionary's table built once and shared, and history that is not contiguous with the block: rcx_*_encode_shared_batch.
+ * Measured on an MI355X, device memory, median of 10 calls at level 6: 4096 x 64 KiB blocks 224.3 ms with hist_len NULL (the level call:
+ * 212.0), linked by 32 KiB 281.7 ms; 65536 x 2 KiB records 259.6 ms alone, 1033.2 ms behind a replicated 32 KiB dictionary
+ * (benchmarks/deflate_hist_rate.py). */
 int rcx_deflate_encode_hist_batch(rcx_ctx*, const rcx_batch*, int level, const uint64_t* hist_len);
 int rcx_zlib_encode_dict_batch(rcx_ctx*, const rcx_batch*, int level, const uint64_t* hist_len, const uint32_t* dict_id);
 uint64_t rcx_deflate_hist_scratch_bytes(uint32_t nblocks, uint64_t max_block);
+/* The encoders behind SHARED DICTIONARIES (extension): many small records behind few dictionaries, without a copy of the dictionary in
+ * front of every record and without rebuilding its hash chains for every record.  dict_off and dict_len are host arrays of nblocks
+ * entries.  The history of block i is the dict_len[i] bytes at in_base + dict_off[i]: anywhere in the input buffer, before or after the
+ * block, overlapping other blocks' input or other dictionaries; read and never written.  dict_len[i] == 0: no dictionary, dict_off[i] is
+ * ignored.  Blocks that name the same range (the same offset and length after the clamp below) share one table, built once per call.
+ * With both arrays NULL the results are rcx_lz4_encode_hc_batch's / rcx_{deflate,zlib}_encode_level_batch's; one NULL and the other not
+ * is RCX_RC_BAD_ARG.
+ * BYTES: every block's output bytes, out_len, in_used and status are exactly what rcx_lz4_encode_hc_hist_batch /
+ * rcx_deflate_encode_hist_batch / rcx_zlib_encode_dict_batch produce at the same level for the same block with the same dict_len[i]
+ * bytes copied directly in front of it -- levels (LZ4 1..12, DEFLATE and zlib 2..9, anything else RCX_RC_BAD_ARG), end rules, bounds,
+ * statuses, determinism, the zlib form's FDICT, FCHECK, dict_id[i] big-endian and the block's own Adler-32 (the slot needs the raw bound
+ * + 10) included.  Of 65536 LZ4 dictionary bytes the first is out of reach: a dictionary is clamped to its last 65535 bytes before
+ * ranges are compared; all 32768 DEFLATE dictionary bytes are within reach.  dict_len[i] above 65536 (LZ4) or 32768 (DEFLATE) is
+ * RCX_RC_BAD_ARG and rcx_last_error names the block.  No emitted distance exceeds position + dict_len[i]; the output depends neither on
+ * the block's place in the batch nor on which other blocks share its dictionary; and NO NEIGHBOURING BYTE influences it, in front of a
+ * dictionary or behind its end: a match whose source starts in the dictionary and runs past its last byte continues in the block's
+ * first bytes.  From RCX_MEM_HOST the span that travels in covers the dictionaries' ranges as well as the blocks'.
+ * SCRATCH: 256 KiB (LZ4; DEFLATE 192 KiB) per DISTINCT dictionary -- its bucket table and its 16-bit links -- and 8 bytes per block
+ * beyond what the encoders without history take: rcx_*_shared_scratch_bytes(nblocks, max_block, ndict), ndict = the distinct
+ * dictionaries.  The batch calls size it themselves.
+ * COST PER BLOCK: the workgroup of a block's first segment copies its dictionary's whole bucket table, 128 KiB, from device memory
+ * into LDS before it links the block (one workgroup a CU), however small the block; for 2 KiB records that copy, not the record, is
+ * most of the call (the times below).  Records much smaller than the table would want several records a workgroup behind one copy,
+ * which is not built.
+ * NOT PROVIDED: decoders that read a dictionary that is not in front of the slot (rcx_inflate_hist_batch, rcx_zlib_decode_dict_batch and
+ * rcx_lz4_decode_linked_batch decode these blocks, given the dictionary in front of the slot: their kernels rest on one contiguous
+ * stream); lz4frame.encode_frames taking this call for independent blocks with a dictionary; level 1, gzip and the greedy LZ4 encoder.
+ * The ids RCX_*_SHARED name the entry points to rcx_ctx_set_variant / rcx_ctx_set_param; rcx_launch_dev does not take them (the
+ * dictionaries' words come from the host's plan).  Measured on an MI355X, device memory, 65536 x 2 KiB text records behind one 32 KiB
+ * dictionary, median of 10 calls: LZ4 HC level 9 83.8 ms (the history call on the replicated layout: 795.5), DEFLATE level 6 272.5 ms
+ * (1033.7); benchmarks/dict_shared_rate.py, DESIGN.md 3.17. */
+int rcx_lz4_encode_hc_shared_batch(rcx_ctx*, const rcx_batch*, int level, const uint64_t* dict_off, const uint64_t* dict_len);
+int rcx_deflate_encode_shared_batch(rcx_ctx*, const rcx_batch*, int level, const uint64_t* dict_off, const uint64_t* dict_len);
+int rcx_zlib_encode_shared_batch(rcx_ctx*, const rcx_batch*, int level, const uint64_t* dict_off, const uint64_t* dict_len, const uint32_t* dict_id);
+uint64_t rcx_lz4_hc_shared_scratch_bytes(uint32_t nblocks, uint64_t max_block, uint32_t ndict);
+uint64_t rcx_deflate_shared_scratch_bytes(uint32_t nblocks, uint64_t max_block, uint32_t ndict);
 /* Inflate with HISTORY (extension; the mirror of dict_len in rcx_lz4_decode_linked_batch).  Stream i decodes into its slot, and its
  * matches may reach into the hist_len[i] (at most 32768, at most out_off[i]; anything else RCX_RC_BAD_ARG naming the block) bytes
  * that lie directly before out_base + out_off[i].  The caller put them there; they are read and never written.  A distance beyond
@@ -400,7 +438,8 @@ enum rcx_codec {
 /* Ids of the batch entry points that rcx_launch_dev, rcx_multi_* and rcx_scratch_bytes do not take (enum rcx_codec stays as it is for
  * those): they name the entry point to rcx_ctx_set_variant / rcx_ctx_set_param, neither of which has a setting for them yet. */
 enum rcx_xcodec { RCX_XXH32 = 32, RCX_LZ4_DECODE_LINKED = 33, RCX_LZ4_ENCODE_HIST = 34, RCX_DEFLATE_ENCODE_HIST = 35, RCX_ZLIB_ENCODE_DICT = 36,
-                  RCX_INFLATE_HIST = 37, RCX_ZLIB_DECODE_DICT = 38, RCX_XCODEC_END = 39 };
+                  RCX_INFLATE_HIST = 37, RCX_ZLIB_DECODE_DICT = 38, RCX_LZ4_ENCODE_SHARED = 39, RCX_DEFLATE_ENCODE_SHARED = 40,
+                  RCX_ZLIB_ENCODE_SHARED = 41, RCX_XCODEC_END = 42 };
 /* scratch bytes (HBM) the codec needs for nblocks blocks of <= max_block bytes.  Required for LZ4 encode, BWT and gzip
  * decode and the DEFLATE / zlib / gzip encoders; for RCX_INFLATE / RCX_ZLIB_DECODE it is what the default (wave-per-stream) decoder needs -- without it
  * rcx_launch_dev falls back to the lane-per-stream kernel (same results, slower on small batches). */

@@ -125,7 +125,10 @@ pub const RCX_DEFLATE_ENCODE_HIST: c_int = 35;
 pub const RCX_ZLIB_ENCODE_DICT: c_int = 36;
 pub const RCX_INFLATE_HIST: c_int = 37;
 pub const RCX_ZLIB_DECODE_DICT: c_int = 38;
-pub const RCX_XCODEC_END: c_int = 39;
+pub const RCX_LZ4_ENCODE_SHARED: c_int = 39;
+pub const RCX_DEFLATE_ENCODE_SHARED: c_int = 40;
+pub const RCX_ZLIB_ENCODE_SHARED: c_int = 41;
+pub const RCX_XCODEC_END: c_int = 42;
 
 #[link(name = "rcx")]
 extern "C" {
@@ -170,6 +173,12 @@ extern "C" {
     pub fn rcx_deflate_hist_scratch_bytes(nblocks: u32, max_block: u64) -> u64;
     pub fn rcx_inflate_hist_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32, hist_len: *const u64) -> c_int;
     pub fn rcx_zlib_decode_dict_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32, hist_len: *const u64, dict_id: *const u32) -> c_int;
+    // ---- the encoders behind shared dictionaries (extension): a range anywhere in the input buffer, its chains built once per call
+    pub fn rcx_lz4_encode_hc_shared_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int, dict_off: *const u64, dict_len: *const u64) -> c_int;
+    pub fn rcx_deflate_encode_shared_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int, dict_off: *const u64, dict_len: *const u64) -> c_int;
+    pub fn rcx_zlib_encode_shared_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int, dict_off: *const u64, dict_len: *const u64, dict_id: *const u32) -> c_int;
+    pub fn rcx_lz4_hc_shared_scratch_bytes(nblocks: u32, max_block: u64, ndict: u32) -> u64;
+    pub fn rcx_deflate_shared_scratch_bytes(nblocks: u32, max_block: u64, ndict: u32) -> u64;
     // ---- BWT / MTF / DC (src/bwt/mod.rs, mtf.rs, dc.rs)
     pub fn rcx_bwt_forward_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;
     pub fn rcx_bwt_suffixes_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;

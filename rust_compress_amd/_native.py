@@ -49,6 +49,8 @@ EXPORTS = [
     "rcx_lz4_encode_hc_hist_batch", "rcx_lz4_hc_hist_scratch_bytes",
     "rcx_deflate_encode_hist_batch", "rcx_zlib_encode_dict_batch", "rcx_deflate_hist_scratch_bytes",
     "rcx_inflate_hist_batch", "rcx_zlib_decode_dict_batch",
+    "rcx_lz4_encode_hc_shared_batch", "rcx_deflate_encode_shared_batch", "rcx_zlib_encode_shared_batch",
+    "rcx_lz4_hc_shared_scratch_bytes", "rcx_deflate_shared_scratch_bytes",
 ]
 
 
@@ -126,6 +128,12 @@ def lib():
         L.rcx_zlib_decode_dict_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p]
         L.rcx_deflate_hist_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64]
         L.rcx_deflate_hist_scratch_bytes.restype = C.c_uint64
+        L.rcx_lz4_encode_hc_shared_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p]
+        L.rcx_deflate_encode_shared_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p]
+        L.rcx_zlib_encode_shared_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("rcx_lz4_hc_shared_scratch_bytes", "rcx_deflate_shared_scratch_bytes"):
+            getattr(L, name).argtypes = [C.c_uint32, C.c_uint64, C.c_uint32]
+            getattr(L, name).restype = C.c_uint64
         L.rcx_deflate_level_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64]
         L.rcx_deflate_level_scratch_bytes.restype = C.c_uint64
         for name in ("rcx_inflate_batch", "rcx_zlib_decode_batch", "rcx_adler32_batch", "rcx_crc32_batch",

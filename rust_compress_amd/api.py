@@ -39,6 +39,27 @@ def _pack_hist(blobs, histories, limit):
     return np.frombuffer(bytes(buf) + b"\0" * 16, np.uint8), off, hl
 
 
+def _pack_shared(blobs, dictionary, limit):
+    """the input buffer of the *_shared calls: every distinct dictionary ONCE (its last `limit` bytes), then the blobs.  dictionary: bytes
+    for all blobs, or a list with one entry (bytes or None) per blob.  -> (uint8 array, in_off, in_len, dict_off, dict_len, the dictionaries
+    per blob)"""
+    dicts = _per_blob(dictionary, len(blobs))
+    buf, at = bytearray(), {}
+    for d in dicts:
+        d = d[-limit:]
+        if d and d not in at:
+            at[d] = len(buf)
+            buf += d
+    off, d_off, d_len = [], [], []
+    for blob, d in zip(blobs, dicts):
+        d = d[-limit:]
+        off.append(len(buf))
+        buf += bytes(blob)
+        d_off.append(at[d] if d else 0)
+        d_len.append(len(d))
+    return np.frombuffer(bytes(buf) + b"\0" * 16, np.uint8), off, [len(b) for b in blobs], d_off, d_len, dicts
+
+
 class RcxError(RuntimeError):
     pass
 
@@ -180,6 +201,66 @@ class Context:
         base = np.frombuffer(bytes(buf) + b"\0" * 16, np.uint8)
         return self.lz4_encode_hc_hist(base, off, [len(b) for b in blobs], hl, level, caps)
 
+    def _shared(self, fn_name, base, in_off, in_len, dict_off, dict_len, level, caps, dict_id=None):
+        """one rcx_*_encode_shared_batch call over a buffer the caller laid out (base: a numpy uint8 array)"""
+        n = len(in_off)
+        off = np.ascontiguousarray(in_off, np.uint64) if n else np.zeros(1, np.uint64)
+        lens = np.ascontiguousarray(in_len, np.uint64) if n else np.zeros(1, np.uint64)
+        total, ooff, ocap = B.layout(caps)
+        out = np.zeros(total, dtype=np.uint8)
+        out_len = np.zeros(max(n, 1), np.uint64)
+        in_used = np.zeros(max(n, 1), np.uint64)
+        status = np.zeros(max(n, 1), np.int32)
+        if (dict_off is None) != (dict_len is None):
+            raise ValueError("dict_off and dict_len: both or neither")
+        d_off = d_len = None
+        if dict_len is not None:
+            d_off = np.ascontiguousarray(dict_off, np.uint64) if n else np.zeros(1, np.uint64)
+            d_len = np.ascontiguousarray(dict_len, np.uint64) if n else np.zeros(1, np.uint64)
+            if n and (d_off.size != n or d_len.size != n):
+                raise ValueError("dict_off, dict_len: one entry per block")
+        if base.size == 0:
+            base = np.zeros(1, np.uint8)
+        p = lambda a: a.ctypes.data
+        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
+        args = [self._h, C.byref(b), int(level), C.c_void_p(p(d_off) if d_off is not None else None), C.c_void_p(p(d_len) if d_len is not None else None)]
+        if dict_id is not None:
+            ids = np.array(list(dict_id) or [0], np.uint32)
+            args.append(C.c_void_p(p(ids)))
+        self._chk(getattr(N.lib(), fn_name)(*args))
+        return Result(B.unpack(out, ooff, out_len[:n]), out_len[:n], in_used[:n], status[:n], None)
+
+    def lz4_encode_hc_shared(self, base, in_off, in_len, dict_off, dict_len, level=9, caps=None):
+        """rcx_lz4_encode_hc_shared_batch over a buffer the caller laid out: block i is base[in_off[i] : in_off[i] + in_len[i]] (base: a
+        numpy uint8 array) and its matches may reach into base[dict_off[i] : dict_off[i] + dict_len[i]] (at most 65536 bytes, anywhere in
+        the buffer; 0: none).  Blocks that name the same range share one table, built once.  The bytes are lz4_encode_hc_hist's for the
+        same block with the same dictionary directly in front of it.  dict_off and dict_len None: lz4_encode_hc_blocks' results."""
+        if caps is None:
+            caps = [max(int(N.lib().rcx_lz4_compression_bound(int(l))), 1) for l in in_len]
+        return self._shared("rcx_lz4_encode_hc_shared_batch", base, in_off, in_len, dict_off, dict_len, level, caps)
+
+    def lz4_encode_hc_dict_blocks(self, blobs, dictionary, level=9, caps=None):
+        """One LZ4 HC block per blob behind a dictionary (bytes for all blobs, or a list with one entry, bytes or None, per blob; the last
+        64 KiB count): equal dictionaries are placed in the input buffer once and their hash chains are built once
+        (rcx_lz4_encode_hc_shared_batch).  The blocks decode as lz4_encode_hc_hist_blocks' do."""
+        base, off, lens, d_off, d_len, _ = _pack_shared(blobs, dictionary, 65536)
+        return self.lz4_encode_hc_shared(base, off, lens, d_off, d_len, level, caps)
+
+    def deflate_encode_shared(self, base, in_off, in_len, dict_off, dict_len, level=6, caps=None):
+        """rcx_deflate_encode_shared_batch (levels 2..9) over a buffer the caller laid out, as lz4_encode_hc_shared: dictionaries of at
+        most 32768 bytes anywhere in the buffer; the bytes are deflate_encode_hist's for the same block with the same dictionary
+        directly in front of it."""
+        if caps is None:
+            caps = [deflate_bound(int(l)) for l in in_len]
+        return self._shared("rcx_deflate_encode_shared_batch", base, in_off, in_len, dict_off, dict_len, level, caps)
+
+    def deflate_encode_dict_blocks(self, blobs, dictionary, level=6, caps=None):
+        """One raw DEFLATE stream per blob (levels 2..9) behind a dictionary (bytes for all blobs, or a list with one entry, bytes or
+        None, per blob; the last 32 KiB count): equal dictionaries are placed in the input buffer once and their hash chains are built
+        once (rcx_deflate_encode_shared_batch).  The streams decode as deflate_encode_hist_blocks' do."""
+        base, off, lens, d_off, d_len, _ = _pack_shared(blobs, dictionary, 32768)
+        return self.deflate_encode_shared(base, off, lens, d_off, d_len, level, caps)
+
     def inflate(self, blobs, caps):
         return self._run_host("rcx_inflate_batch", blobs, caps, extra_out=True)
 
@@ -249,13 +330,19 @@ class Context:
         rcx_deflate_compression_bound.  level 1..9 (rcx_deflate_encode_level_batch; 1 is the default encoder's bytes)."""
         return self._deflate_encode("rcx_deflate_encode", blobs, caps, 0, level)
 
-    def zlib_encode(self, blobs, caps=None, level=1, zdict=None):
+    def zlib_encode(self, blobs, caps=None, level=1, zdict=None, shared=False):
         """One zlib stream (RFC 1950: 78 01 at level 1, DEFLATE, Adler-32) per blob; caps default to the DEFLATE bound + 6.
         zdict (bytes for all blobs, or a list with one entry, bytes or None, per blob; levels 2..9): a preset dictionary as Python's
         zlib takes it (rcx_zlib_encode_dict_batch) -- its last 32 KiB are placed in front of every block, the stream carries FDICT and
-        DICTID = zlib.adler32(zdict), and caps default to the bound + 10."""
+        DICTID = zlib.adler32(zdict), and caps default to the bound + 10.  shared=True: the same streams from
+        rcx_zlib_encode_shared_batch -- equal dictionaries lie in the input buffer once and their hash chains are built once."""
         if zdict is None:
             return self._deflate_encode("rcx_zlib_encode", blobs, caps, 6, level)
+        if shared:
+            base, off, lens, d_off, d_len, dicts = _pack_shared(blobs, zdict, 32768)
+            if caps is None:
+                caps = [deflate_bound(n) + 10 for n in lens]
+            return self._shared("rcx_zlib_encode_shared_batch", base, off, lens, d_off, d_len, level, caps, [_adler32(d) for d in dicts])
         dicts = _per_blob(zdict, len(blobs))
         base, off, hl = _pack_hist(blobs, dicts, 32768)
         return self._deflate_hist(base, off, [len(b) for b in blobs], hl, level, caps, [_adler32(d) for d in dicts])

@@ -171,6 +171,16 @@ extern "C" uint64_t rcx_deflate_hist_scratch_bytes(uint32_t nblocks, uint64_t ma
     return rcx_tu_deflate_hist_scratch(nblocks, (uint64_t)nblocks * rcx_tu_deflate_encode_segments(max_block), nblocks);
 }
 
+// (ndict: the distinct dictionaries, 256 KiB each at the most; every block counted at max_block)
+extern "C" uint64_t rcx_lz4_hc_shared_scratch_bytes(uint32_t nblocks, uint64_t max_block, uint32_t ndict)
+{
+    return rcx_tu_lz4_hc_dict_scratch(nblocks, (uint64_t)nblocks * rcx_tu_lz4_hc_segments(max_block), ndict);
+}
+extern "C" uint64_t rcx_deflate_shared_scratch_bytes(uint32_t nblocks, uint64_t max_block, uint32_t ndict)
+{
+    return rcx_tu_deflate_dict_scratch(nblocks, (uint64_t)nblocks * rcx_tu_deflate_encode_segments(max_block), ndict);
+}
+
 // ---- scratch requirements ---------------------------------------------------------------------
 extern "C" uint64_t rcx_scratch_bytes(int codec, uint32_t nblocks, uint64_t max_block)
 {
@@ -202,8 +212,9 @@ struct rcx_call {
     bool needs_out;
     uint32_t seed;                       // XXH32
     const link_tables* link;             // linked LZ4 decode, else null
-    uint32_t nhist;                      // LZ4 HC / DEFLATE encode with history: the blocks that have one (their lengths are aux_in)
-    uint32_t aux_words;                  // words per block of aux_in: 1, or 2 (the zlib calls with history: lengths, then DICTIDs)
+    uint32_t nhist;                      // LZ4 HC / DEFLATE encode with history: the blocks that have one (their lengths are aux_in); behind shared dictionaries: the distinct dictionaries
+    uint32_t aux_words;                  // words per block of aux_in: 1, or 2 (the zlib calls with history: lengths, then DICTIDs), or RCX_DICT_WORDS
+    uint64_t dict_span;                  // shared dictionaries: one past their highest byte in the input buffer (it travels in with the blocks)
 };
 
 // ---- per-codec traits of the host path ------------------------------------------------------------------------------------------------
@@ -213,6 +224,7 @@ enum scratch_rule { SCRATCH_BY_CODEC,                                  // rcx_sc
                     SCRATCH_HC_SEGS,                                   // HC: the chains and parse of the real segments
                     SCRATCH_HC_HIST_SEGS,                              // ... and the chains of the real histories
                     SCRATCH_DEFLATE_HIST_SEGS,                         // DEFLATE levels 2..9: the real segments and the real histories
+                    SCRATCH_HC_DICT_SEGS, SCRATCH_DEFLATE_DICT_SEGS,   // the real segments and the distinct dictionaries
                     SCRATCH_DC_OPTIONAL };                             // chunk states: none with contexts, and none when they cannot be had
 enum back_policy { BACK_USED_SPAN, BACK_INFLATE /* mirrored: the streams the first pass handed back */, BACK_CHAINS };
 struct codec_traits {
@@ -240,6 +252,8 @@ static codec_traits traits_of(int codec, uint32_t param)
     case RCX_LZ4_ENCODE: if (param) { t.preload_out = true; t.scratch = SCRATCH_HC_SEGS; } break;
     case RCX_LZ4_ENCODE_HIST: t.preload_out = true; t.scratch = SCRATCH_HC_HIST_SEGS; break;
     case RCX_DEFLATE_ENCODE_HIST: case RCX_ZLIB_ENCODE_DICT: t.preload_out = true; t.scratch = SCRATCH_DEFLATE_HIST_SEGS; break;
+    case RCX_LZ4_ENCODE_SHARED: t.preload_out = true; t.scratch = SCRATCH_HC_DICT_SEGS; break;
+    case RCX_DEFLATE_ENCODE_SHARED: case RCX_ZLIB_ENCODE_SHARED: t.preload_out = true; t.scratch = SCRATCH_DEFLATE_DICT_SEGS; break;
     // the decoders with history read the bytes the caller put in front of the slots: the staged output span starts as the caller's
     case RCX_INFLATE_HIST: case RCX_ZLIB_DECODE_DICT: t.preload_out = true; break;
     case RCX_DC_ENCODE: t.scratch = SCRATCH_DC_OPTIONAL; break;
@@ -251,7 +265,7 @@ static codec_traits traits_of(int codec, uint32_t param)
 }
 static rcx_call call_of(int codec, uint32_t param = 0, const uint32_t* aux_in = nullptr, uint32_t* aux_out = nullptr, const uint64_t* n_out = nullptr)
 {
-    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr, 0, 1};
+    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr, 0, 1, 0};
 }
 
 // ---- kernel arguments: built here and nowhere else ---------------------------------------------------------------------------------------
@@ -316,6 +330,14 @@ static int launch_codec(rcx_ctx* c, const rcx_call& call, rcx_kargs& k)
         break; }
     case RCX_LZ4_ENCODE_HIST: {                                  // the codec parameter: the HC level; k.aux: the history lengths
         int rc = rcx_tu_lz4_hc_hist(s, k, (int)call.param, call.nhist, c->err);
+        if (rc) return rc;
+        break; }
+    case RCX_LZ4_ENCODE_SHARED: {                                // the codec parameter: the HC level; k.aux: the words of rcx_plan_dict
+        int rc = rcx_tu_lz4_hc_dict(s, k, (int)call.param, call.nhist, c->err);
+        if (rc) return rc;
+        break; }
+    case RCX_DEFLATE_ENCODE_SHARED: case RCX_ZLIB_ENCODE_SHARED: {   // the codec parameter: the level, 2..9; k.aux: the words of rcx_plan_dict
+        int rc = rcx_tu_deflate_encode_dict(s, k, codec == RCX_ZLIB_ENCODE_SHARED ? 1 : 0, (int)call.param, call.nhist, c->err);
         if (rc) return rc;
         break; }
     case RCX_INFLATE:
@@ -432,6 +454,7 @@ static int check_batch(rcx_ctx* c, const rcx_call& call, const rcx_batch* b, bat
     HIPCHK(c, hipSetDevice(c->device));
     if (!rcx_plan_spans(st.n, b->in_off, b->in_len, call.needs_out ? b->out_off : nullptr, call.needs_out ? b->out_cap : nullptr, st.sp, c->err))
         return RCX_RC_BAD_ARG;
+    if (call.dict_span > st.sp.in_span) st.sp.in_span = call.dict_span;      // (the dictionaries' ranges travel in with the blocks')
     if ((st.sp.in_span && !b->in_base) || (st.sp.out_span && !b->out_base)) { c->err = "null data pointer"; return RCX_RC_BAD_ARG; }
     if (b->mem != RCX_MEM_HOST && b->mem != RCX_MEM_DEVICE) { c->err = "bad mem kind"; return RCX_RC_BAD_ARG; }
     return RCX_RC_OK;
@@ -555,6 +578,14 @@ static int reserve_scratch(rcx_ctx* c, const rcx_call& call, batch_state& st)
     case SCRATCH_DEFLATE_HIST_SEGS:
         for (uint32_t i = 0; i < n; i++) segs += rcx_tu_deflate_encode_segments(b->in_len[i]);
         sb = rcx_tu_deflate_hist_scratch(n, segs, call.nhist);
+        break;
+    case SCRATCH_HC_DICT_SEGS:
+        for (uint32_t i = 0; i < n; i++) segs += rcx_tu_lz4_hc_segments(b->in_len[i]);
+        sb = rcx_tu_lz4_hc_dict_scratch(n, segs, call.nhist);
+        break;
+    case SCRATCH_DEFLATE_DICT_SEGS:
+        for (uint32_t i = 0; i < n; i++) segs += rcx_tu_deflate_encode_segments(b->in_len[i]);
+        sb = rcx_tu_deflate_dict_scratch(n, segs, call.nhist);
         break;
     case SCRATCH_DC_OPTIONAL:                                       // withctx: the wave-per-block kernel encodes, no chunk states
         sb = call.param ? 0 : rcx_scratch_bytes(call.codec, n, st.sp.max_block);
@@ -852,6 +883,39 @@ extern "C" int rcx_deflate_encode_hist_batch(rcx_ctx* c, const rcx_batch* b, int
 extern "C" int rcx_zlib_encode_dict_batch(rcx_ctx* c, const rcx_batch* b, int level, const uint64_t* hist_len, const uint32_t* dict_id)
 {
     return deflate_hist_batch(c, RCX_ZLIB_ENCODE_DICT, b, level, hist_len, dict_id);
+}
+// The encoders behind SHARED DICTIONARIES: block i's history is a range anywhere in the input buffer, and the chains of a range are built
+// once for all the blocks that name it (csrc/lz_dict.h).  rcx_plan_dict checks the lengths, clamps and maps blocks to distinct ranges; its
+// words go to the kernels in the descriptors' aux array, and the span of the ranges widens what travels in from host memory.
+static int shared_batch(rcx_ctx* c, int codec, const rcx_batch* b, int level, const uint64_t* dict_off, const uint64_t* dict_len, const uint32_t* dict_id)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    const bool lz4 = codec == RCX_LZ4_ENCODE_SHARED;
+    if (lz4 && (level < 1 || level > 12)) { c->err = "lz4 hc: level must be 1..12"; return RCX_RC_BAD_ARG; }
+    if (!lz4 && (level < 2 || level > 9)) { c->err = "deflate encode behind shared dictionaries: level must be 2..9 (level 1 has none)"; return RCX_RC_BAD_ARG; }
+    if (!dict_off != !dict_len) { c->err = "shared dictionaries: dict_off and dict_len come together or not at all"; return RCX_RC_BAD_ARG; }
+    if (!dict_len)                                               // the encoders without history
+        return run_batch(c, call_of(lz4 ? RCX_LZ4_ENCODE : codec == RCX_ZLIB_ENCODE_SHARED ? RCX_ZLIB_ENCODE : RCX_DEFLATE_ENCODE, (uint32_t)level), b);
+    rcx_call call = call_of(codec, (uint32_t)level);
+    if (!b || !b->nblocks) return run_batch(c, call, b);
+    if (codec == RCX_ZLIB_ENCODE_SHARED && !dict_id) { c->err = "zlib encode behind shared dictionaries: null dict_id array"; return RCX_RC_BAD_ARG; }
+    rcx_dict_plan plan;
+    if (!rcx_plan_dict(b->nblocks, dict_off, dict_len, lz4 ? 65536 : 32768, lz4 ? 65535 : 32768, dict_id, lz4 ? "lz4 hc" : "deflate encode", plan, c->err))
+        return RCX_RC_BAD_ARG;
+    call.aux_in = plan.aux.data(); call.aux_words = RCX_DICT_WORDS; call.nhist = plan.ndict; call.dict_span = plan.span;
+    return run_batch(c, call, b);                                // (waits for the stream: the words above may go)
+}
+extern "C" int rcx_lz4_encode_hc_shared_batch(rcx_ctx* c, const rcx_batch* b, int level, const uint64_t* dict_off, const uint64_t* dict_len)
+{
+    return shared_batch(c, RCX_LZ4_ENCODE_SHARED, b, level, dict_off, dict_len, nullptr);
+}
+extern "C" int rcx_deflate_encode_shared_batch(rcx_ctx* c, const rcx_batch* b, int level, const uint64_t* dict_off, const uint64_t* dict_len)
+{
+    return shared_batch(c, RCX_DEFLATE_ENCODE_SHARED, b, level, dict_off, dict_len, nullptr);
+}
+extern "C" int rcx_zlib_encode_shared_batch(rcx_ctx* c, const rcx_batch* b, int level, const uint64_t* dict_off, const uint64_t* dict_len, const uint32_t* dict_id)
+{
+    return shared_batch(c, RCX_ZLIB_ENCODE_SHARED, b, level, dict_off, dict_len, dict_id);
 }
 // Inflate with history: the history lies in front of the slot in the OUTPUT buffer and is staged with it (preload_out).  Without
 // lengths the call is the plain one.

@@ -2,6 +2,7 @@
 // gated launch, the chains of a linked LZ4 batch, and what travels back.  Plain C++17, no HIP: tests/host_plan drives it on the CPU.
 #pragma once
 #include <stdint.h>
+#include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
@@ -151,6 +152,50 @@ inline bool rcx_plan_hist(uint32_t n, const uint64_t* hist_len, const uint64_t* 
         aux[i] = (uint32_t)hist_len[i];
         nhist += hist_len[i] ? 1u : 0u;
         if (ids) aux[(size_t)n + i] = ids[i];
+    }
+    return true;
+}
+
+// ---- shared dictionaries (the encoders' *_shared_batch calls) -----------------------------------------------------------------------------
+// Block i's history is the dict_len[i] bytes at dict_off[i] of the input buffer, anywhere in it; dict_len[i] == 0: none, dict_off[i]
+// ignored.  At most max_dict bytes (false: `err`, prefixed with `what`, names the block), of which the last `reach` count: a longer one
+// is clamped to them, and blocks whose ranges are equal AFTER the clamp share one dictionary (ranges that overlap but differ do not).
+// aux: the kernels' words, RCX_DICT_WORDS per block, laid out by csrc/lz_dict.h: [0, n) the clamped length, [n, 2n) ids[i] (ids != null:
+// the zlib form), [2n, 3n) the dictionary's index among the distinct ones, [3n, 5n) its offset (low words, then high words), [5n,
+// 5n + ndict) a block that names dictionary j (the rest of [5n, 6n): n, no block).  span: one past the highest dictionary byte.  n > 0.
+static const uint32_t RCX_DICT_WORDS = 6;
+struct rcx_dict_plan {
+    std::vector<uint32_t> aux;
+    uint32_t ndict = 0;
+    uint64_t span = 0;
+};
+inline bool rcx_plan_dict(uint32_t n, const uint64_t* dict_off, const uint64_t* dict_len, uint64_t max_dict, uint64_t reach, const uint32_t* ids,
+                          const char* what, rcx_dict_plan& p, std::string& err)
+{
+    const size_t N = n;
+    p.aux.assign(RCX_DICT_WORDS * N, 0);
+    for (size_t i = 0; i < N; i++) p.aux[5 * N + i] = n;
+    p.ndict = 0; p.span = 0;
+    std::vector<std::pair<std::pair<uint64_t, uint64_t>, uint32_t>> named;       // (offset, length) after the clamp, block
+    for (uint32_t i = 0; i < n; i++) {
+        if (ids) p.aux[N + i] = ids[i];
+        uint64_t len = dict_len[i], off = len ? dict_off[i] : 0;
+        if (len > max_dict || off + len < off) {
+            err = std::string(what) + ": block " + std::to_string(i) + ": a dictionary of " + std::to_string(len) + " bytes "
+                + (len > max_dict ? "(at most " + std::to_string(max_dict) + ")" : "at offset " + std::to_string(off) + " wraps");
+            return false;
+        }
+        if (!len) continue;
+        if (off + len > p.span) p.span = off + len;
+        if (len > reach) { off += len - reach; len = reach; }
+        p.aux[i] = (uint32_t)len;
+        p.aux[3 * N + i] = (uint32_t)off; p.aux[4 * N + i] = (uint32_t)(off >> 32);
+        named.push_back({{off, len}, i});
+    }
+    std::sort(named.begin(), named.end());                                        // equal ranges side by side, their lowest block first
+    for (size_t k = 0; k < named.size(); k++) {
+        if (!k || named[k].first != named[k - 1].first) p.aux[5 * N + p.ndict++] = named[k].second;
+        p.aux[2 * N + named[k].second] = p.ndict - 1;
     }
     return true;
 }

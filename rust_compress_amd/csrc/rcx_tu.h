@@ -44,6 +44,9 @@ uint64_t rcx_tu_deflate_level_scratch(uint32_t nblocks, uint64_t nsegs);
 // nhist = the blocks that have one
 int rcx_tu_deflate_encode_hist(hipStream_t s, rcx_kargs& k, int fmt, int level, uint32_t nhist, std::string& err);
 uint64_t rcx_tu_deflate_hist_scratch(uint32_t nblocks, uint64_t nsegs, uint64_t nhist);
+// ... levels 2..9 behind shared dictionaries (k_deflate_hc_dict.hip), fmt 0 or 1: k.aux = the words of rcx_plan_dict, ndict = the distinct dictionaries
+int rcx_tu_deflate_encode_dict(hipStream_t s, rcx_kargs& k, int fmt, int level, uint32_t ndict, std::string& err);
+uint64_t rcx_tu_deflate_dict_scratch(uint32_t nblocks, uint64_t nsegs, uint64_t ndict);
 // tu_lz4_hc.hip (level 1..12)
 int rcx_tu_lz4_hc(hipStream_t s, rcx_kargs& k, int level, std::string& err);
 uint64_t rcx_tu_lz4_hc_scratch(uint32_t nblocks, uint64_t nsegs);
@@ -51,6 +54,9 @@ uint64_t rcx_tu_lz4_hc_segments(uint64_t len);
 // ... with history (k_lz4_hc_hist.hip): k.aux = the history lengths (uint32) or null, nhist = the blocks that have one
 int rcx_tu_lz4_hc_hist(hipStream_t s, rcx_kargs& k, int level, uint32_t nhist, std::string& err);
 uint64_t rcx_tu_lz4_hc_hist_scratch(uint32_t nblocks, uint64_t nsegs, uint64_t nhist);
+// ... behind shared dictionaries (k_lz4_hc_dict.hip): k.aux = the words of rcx_plan_dict, ndict = the distinct dictionaries
+int rcx_tu_lz4_hc_dict(hipStream_t s, rcx_kargs& k, int level, uint32_t ndict, std::string& err);
+uint64_t rcx_tu_lz4_hc_dict_scratch(uint32_t nblocks, uint64_t nsegs, uint64_t ndict);
 // tu_lz4_frame.hip: XXH32 of every block; LZ4 block decode with history (linked blocks, dictionaries), one launch per chain depth
 void rcx_tu_xxh32(hipStream_t s, rcx_kargs& k, uint32_t seed);
 // order[rounds_off[r] .. rounds_off[r + 1]): the blocks at depth r of their chains (rounds_off is a HOST array); head[i]: block i's chain
