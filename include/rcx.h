@@ -304,9 +304,11 @@ uint64_t rcx_deflate_hist_scratch_bytes(uint32_t nblocks, uint64_t max_block);
  * into LDS before it links the block (one workgroup a CU), however small the block; for 2 KiB records that copy, not the record, is
  * most of the call (the times below).  Records much smaller than the table would want several records a workgroup behind one copy,
  * which is not built.
- * NOT PROVIDED: decoders that read a dictionary that is not in front of the slot (rcx_inflate_hist_batch, rcx_zlib_decode_dict_batch and
- * rcx_lz4_decode_linked_batch decode these blocks, given the dictionary in front of the slot: their kernels rest on one contiguous
- * stream); lz4frame.encode_frames taking this call for independent blocks with a dictionary; level 1, gzip and the greedy LZ4 encoder.
+ * The blocks decode behind the same ranges with rcx_lz4_decode_shared_batch / rcx_inflate_shared_batch / rcx_zlib_decode_shared_batch
+ * below (or, given the dictionary in front of the slot, with rcx_lz4_decode_linked_batch / rcx_inflate_hist_batch /
+ * rcx_zlib_decode_dict_batch).
+ * NOT PROVIDED: lz4frame.encode_frames taking this call for independent blocks with a dictionary; level 1, gzip and the greedy LZ4
+ * encoder.
  * The ids RCX_*_SHARED name the entry points to rcx_ctx_set_variant / rcx_ctx_set_param; rcx_launch_dev does not take them (the
  * dictionaries' words come from the host's plan).  Measured on an MI355X, device memory, 65536 x 2 KiB text records behind one 32 KiB
  * dictionary, median of 10 calls: LZ4 HC level 9 83.8 ms (the history call on the replicated layout: 795.5), DEFLATE level 6 272.5 ms
@@ -316,6 +318,47 @@ int rcx_deflate_encode_shared_batch(rcx_ctx*, const rcx_batch*, int level, const
 int rcx_zlib_encode_shared_batch(rcx_ctx*, const rcx_batch*, int level, const uint64_t* dict_off, const uint64_t* dict_len, const uint32_t* dict_id);
 uint64_t rcx_lz4_hc_shared_scratch_bytes(uint32_t nblocks, uint64_t max_block, uint32_t ndict);
 uint64_t rcx_deflate_shared_scratch_bytes(uint32_t nblocks, uint64_t max_block, uint32_t ndict);
+/* The decoders behind SHARED DICTIONARIES (extension): the mirror of the three encoders above -- many small records read behind few
+ * dictionaries without a copy of the dictionary in front of every output slot.  dict_off and dict_len are host arrays of nblocks
+ * entries.  The history of block i is the dict_len[i] bytes at in_base + dict_off[i], in the INPUT buffer beside the compressed blocks:
+ * before or after them, overlapping other dictionaries or other blocks' input; read and never written.  dict_len[i] == 0: no
+ * dictionary, dict_off[i] is ignored.  out_off[i] is free: it may be 0, or smaller than dict_len[i] (which the history calls refuse),
+ * and no address below out_base + out_off[i] is dereferenced for block i.
+ * BYTES: for every block the output bytes [out_off[i], out_off[i] + out_len[i]), out_len, in_used, status and (the DEFLATE forms)
+ * flags are exactly what the history decoder produces for the same block with the same dictionary bytes copied directly in front of
+ * its slot -- rcx_lz4_decode_linked_batch with link all 0 and the same dict_len[i], rcx_inflate_hist_batch, rcx_zlib_decode_dict_batch
+ * with the same dict_id -- for malformed input too.  So: an LZ4 dictionary is at most 65536 bytes, of which the last 65535 count; a
+ * DEFLATE dictionary at most 32768, all within reach; a longer dict_len[i] returns RCX_RC_BAD_ARG and rcx_last_error names the block.
+ * A distance of exactly output so far + dictionary reaches the dictionary's first byte; one more is RCX_E_MALFORMED (LZ4) or
+ * RCX_E_INVALID_HUFFMAN_CODE (DEFLATE), whatever lies in front of the dictionary in memory.  A match whose source starts in the
+ * dictionary and runs past its last byte continues in the block's own first bytes (which may be the ones the match itself produces),
+ * never in what follows the dictionary in the buffer: no byte outside [dict_off, dict_off + dict_len) and the block's own input is
+ * loaded on the dictionary's behalf, and a dictionary may end at the buffer's last byte.  The zlib form: FDICT, DICTID,
+ * RCX_E_ZLIB_DICT, RCX_E_ZLIB_DICT_ID, "no FDICT: the dictionary is ignored" and the Adler-32 of the block alone as in
+ * rcx_zlib_decode_dict_batch.  Nothing outside [out_off[i], out_off[i] + out_cap[i]) is written; the results depend neither on a
+ * block's place in the batch nor on which other blocks name its dictionary.
+ * With both arrays NULL the call is rcx_lz4_decode_batch / rcx_inflate_batch / rcx_zlib_decode_batch; one NULL and the other not is
+ * RCX_RC_BAD_ARG, and so is the zlib form with dictionaries and a NULL dict_id.
+ * From RCX_MEM_HOST the span that travels in covers the dictionaries' ranges as well as the blocks'; nothing of the output buffer
+ * travels in, and only what was produced travels back (the history calls stage the whole output buffer, or every replica of the
+ * dictionary, in).  No scratch beyond the plain decoders': nothing is built per dictionary.
+ * KERNELS: DEFLATE / zlib one lane per stream (k_inflate_hist's kernel with a split far source, k_inflate_dict.hip); LZ4 one wave per
+ * block, parsed wave-uniformly and copied 64 lanes wide straight between device memory and registers, no LDS window
+ * (k_lz4_dict.hip) -- rcx_lz4_decode_linked_batch runs k_lz4_decode_v4's windowed decoder.
+ * NOT PROVIDED: LZ4 chains (`link`) whose head names a shared dictionary; lz4frame.py taking these calls; dictionary streams through
+ * the wave-per-stream inflate kernel; rcx_launch_dev taking the ids RCX_*_DECODE_SHARED / RCX_INFLATE_SHARED (the dictionaries' words
+ * come from the host's plan: a device-resident batch goes through these calls with RCX_MEM_DEVICE, as for the encoders).
+ * Measured on an MI355X, 65536 x 2 KiB text records behind one 32 KiB dictionary (LZ4 HC level 9, DEFLATE level 6), median of 10
+ * calls, the history call on the replicated layout against the shared call: from pageable host memory LZ4 1627.4 against 6.9 ms
+ * (2.18 GB of replicas in 65536 copies against 35.4 MB) and DEFLATE 86.1 against 8.0 ms (2.31 GB in and 2.28 GB out against 28.5 MB
+ * and 134 MB); output buffer 2 281 701 376 against 134 217 728 bytes.  DEVICE-RESIDENT THE SHARED CALLS ARE SLOWER: LZ4 2.504
+ * against 0.920 ms (2.7 times: one sequence at a time, each behind an L2 round trip, where k_lz4_decode_v4 executes batches of 64
+ * sequences in an LDS window), DEFLATE 4.832 against 4.213 ms (the position test in front of every far gather).  No LDS window was
+ * built: it would not take the dictionary and literal loads out of a sequence's chain (benchmarks/dict_decode_rate.py, DESIGN.md
+ * 3.18). */
+int rcx_lz4_decode_shared_batch(rcx_ctx*, const rcx_batch*, const uint64_t* dict_off, const uint64_t* dict_len);
+int rcx_inflate_shared_batch(rcx_ctx*, const rcx_batch*, uint32_t* flags, const uint64_t* dict_off, const uint64_t* dict_len);
+int rcx_zlib_decode_shared_batch(rcx_ctx*, const rcx_batch*, uint32_t* flags, const uint64_t* dict_off, const uint64_t* dict_len, const uint32_t* dict_id);
 /* Inflate with HISTORY (extension; the mirror of dict_len in rcx_lz4_decode_linked_batch).  Stream i decodes into its slot, and its
  * matches may reach into the hist_len[i] (at most 32768, at most out_off[i]; anything else RCX_RC_BAD_ARG naming the block) bytes
  * that lie directly before out_base + out_off[i].  The caller put them there; they are read and never written.  A distance beyond
@@ -439,7 +482,8 @@ enum rcx_codec {
  * those): they name the entry point to rcx_ctx_set_variant / rcx_ctx_set_param, neither of which has a setting for them yet. */
 enum rcx_xcodec { RCX_XXH32 = 32, RCX_LZ4_DECODE_LINKED = 33, RCX_LZ4_ENCODE_HIST = 34, RCX_DEFLATE_ENCODE_HIST = 35, RCX_ZLIB_ENCODE_DICT = 36,
                   RCX_INFLATE_HIST = 37, RCX_ZLIB_DECODE_DICT = 38, RCX_LZ4_ENCODE_SHARED = 39, RCX_DEFLATE_ENCODE_SHARED = 40,
-                  RCX_ZLIB_ENCODE_SHARED = 41, RCX_XCODEC_END = 42 };
+                  RCX_ZLIB_ENCODE_SHARED = 41, RCX_LZ4_DECODE_SHARED = 42, RCX_INFLATE_SHARED = 43, RCX_ZLIB_DECODE_SHARED = 44,
+                  RCX_XCODEC_END = 45 };
 /* scratch bytes (HBM) the codec needs for nblocks blocks of <= max_block bytes.  Required for LZ4 encode, BWT and gzip
  * decode and the DEFLATE / zlib / gzip encoders; for RCX_INFLATE / RCX_ZLIB_DECODE it is what the default (wave-per-stream) decoder needs -- without it
  * rcx_launch_dev falls back to the lane-per-stream kernel (same results, slower on small batches). */

@@ -128,7 +128,10 @@ pub const RCX_ZLIB_DECODE_DICT: c_int = 38;
 pub const RCX_LZ4_ENCODE_SHARED: c_int = 39;
 pub const RCX_DEFLATE_ENCODE_SHARED: c_int = 40;
 pub const RCX_ZLIB_ENCODE_SHARED: c_int = 41;
-pub const RCX_XCODEC_END: c_int = 42;
+pub const RCX_LZ4_DECODE_SHARED: c_int = 42;
+pub const RCX_INFLATE_SHARED: c_int = 43;
+pub const RCX_ZLIB_DECODE_SHARED: c_int = 44;
+pub const RCX_XCODEC_END: c_int = 45;
 
 #[link(name = "rcx")]
 extern "C" {
@@ -179,6 +182,10 @@ extern "C" {
     pub fn rcx_zlib_encode_shared_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int, dict_off: *const u64, dict_len: *const u64, dict_id: *const u32) -> c_int;
     pub fn rcx_lz4_hc_shared_scratch_bytes(nblocks: u32, max_block: u64, ndict: u32) -> u64;
     pub fn rcx_deflate_shared_scratch_bytes(nblocks: u32, max_block: u64, ndict: u32) -> u64;
+    // ---- the decoders behind shared dictionaries (extension): the mirror of the three calls above
+    pub fn rcx_lz4_decode_shared_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, dict_off: *const u64, dict_len: *const u64) -> c_int;
+    pub fn rcx_inflate_shared_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32, dict_off: *const u64, dict_len: *const u64) -> c_int;
+    pub fn rcx_zlib_decode_shared_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32, dict_off: *const u64, dict_len: *const u64, dict_id: *const u32) -> c_int;
     // ---- BWT / MTF / DC (src/bwt/mod.rs, mtf.rs, dc.rs)
     pub fn rcx_bwt_forward_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;
     pub fn rcx_bwt_suffixes_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;

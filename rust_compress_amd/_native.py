@@ -51,6 +51,7 @@ EXPORTS = [
     "rcx_inflate_hist_batch", "rcx_zlib_decode_dict_batch",
     "rcx_lz4_encode_hc_shared_batch", "rcx_deflate_encode_shared_batch", "rcx_zlib_encode_shared_batch",
     "rcx_lz4_hc_shared_scratch_bytes", "rcx_deflate_shared_scratch_bytes",
+    "rcx_lz4_decode_shared_batch", "rcx_inflate_shared_batch", "rcx_zlib_decode_shared_batch",
 ]
 
 
@@ -131,6 +132,9 @@ def lib():
         L.rcx_lz4_encode_hc_shared_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p]
         L.rcx_deflate_encode_shared_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p]
         L.rcx_zlib_encode_shared_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rcx_lz4_decode_shared_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p]
+        L.rcx_inflate_shared_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rcx_zlib_decode_shared_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("rcx_lz4_hc_shared_scratch_bytes", "rcx_deflate_shared_scratch_bytes"):
             getattr(L, name).argtypes = [C.c_uint32, C.c_uint64, C.c_uint32]
             getattr(L, name).restype = C.c_uint64

@@ -261,15 +261,79 @@ class Context:
         base, off, lens, d_off, d_len, _ = _pack_shared(blobs, dictionary, 32768)
         return self.deflate_encode_shared(base, off, lens, d_off, d_len, level, caps)
 
+    def _shared_decode(self, fn_name, base, in_off, in_len, dict_off, dict_len, caps, flags=False, dict_id=None):
+        """one rcx_*_shared_batch decode over a buffer the caller laid out (base: a numpy uint8 array).  Nothing lies in front of a slot."""
+        n = len(in_off)
+        off = np.ascontiguousarray(in_off, np.uint64) if n else np.zeros(1, np.uint64)
+        lens = np.ascontiguousarray(in_len, np.uint64) if n else np.zeros(1, np.uint64)
+        total, ooff, ocap = B.layout(caps)
+        out = np.zeros(total, dtype=np.uint8)
+        out_len = np.zeros(max(n, 1), np.uint64)
+        in_used = np.zeros(max(n, 1), np.uint64)
+        status = np.zeros(max(n, 1), np.int32)
+        if (dict_off is None) != (dict_len is None):
+            raise ValueError("dict_off and dict_len: both or neither")
+        d_off = d_len = None
+        if dict_len is not None:
+            d_off = np.ascontiguousarray(dict_off, np.uint64) if n else np.zeros(1, np.uint64)
+            d_len = np.ascontiguousarray(dict_len, np.uint64) if n else np.zeros(1, np.uint64)
+            if n and (d_off.size != n or d_len.size != n):
+                raise ValueError("dict_off, dict_len: one entry per block")
+        if base.size == 0:
+            base = np.zeros(1, np.uint8)
+        p = lambda a: a.ctypes.data
+        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
+        args = [self._h, C.byref(b)]
+        aux = None
+        if flags:
+            aux = np.zeros(max(n, 1), np.uint32)
+            args.append(C.c_void_p(p(aux)))
+        args += [C.c_void_p(p(d_off) if d_off is not None else None), C.c_void_p(p(d_len) if d_len is not None else None)]
+        if dict_id is not None:
+            ids = np.array(list(dict_id) or [0], np.uint32)
+            args.append(C.c_void_p(p(ids)))
+        self._chk(getattr(N.lib(), fn_name)(*args))
+        return Result(B.unpack(out, ooff, out_len[:n]), out_len[:n], in_used[:n], status[:n], aux[:n] if aux is not None else None)
+
+    def lz4_decode_shared(self, base, in_off, in_len, dict_off, dict_len, caps):
+        """rcx_lz4_decode_shared_batch over a buffer the caller laid out: block i is base[in_off[i] : in_off[i] + in_len[i]] (base: a
+        numpy uint8 array) and its matches may reach into base[dict_off[i] : dict_off[i] + dict_len[i]] (at most 65536 bytes, anywhere in
+        the buffer; 0: none).  The results are those of a decode with the dictionary directly in front of the slot
+        (rcx_lz4_decode_linked_batch with dict_len).  dict_off and dict_len None: lz4_decode_blocks' results."""
+        return self._shared_decode("rcx_lz4_decode_shared_batch", base, in_off, in_len, dict_off, dict_len, caps)
+
+    def lz4_decode_dict_blocks(self, blobs, dictionary, caps):
+        """One LZ4 block per blob, decoded behind a dictionary (bytes for all blobs, or a list with one entry, bytes or None, per blob; the
+        last 64 KiB count): equal dictionaries are placed in the input buffer once, none in front of the slots
+        (rcx_lz4_decode_shared_batch).  What lz4_encode_hc_dict_blocks and lz4_encode_hc_hist_blocks write."""
+        base, off, lens, d_off, d_len, _ = _pack_shared(blobs, dictionary, 65536)
+        return self.lz4_decode_shared(base, off, lens, d_off, d_len, caps)
+
+    def inflate_shared(self, base, in_off, in_len, dict_off, dict_len, caps):
+        """rcx_inflate_shared_batch over a buffer the caller laid out, as lz4_decode_shared: dictionaries of at most 32768 bytes anywhere
+        in the buffer; the results (aux: the flags) are inflate_hist_blocks' for the same dictionary directly in front of the slot."""
+        return self._shared_decode("rcx_inflate_shared_batch", base, in_off, in_len, dict_off, dict_len, caps, flags=True)
+
+    def inflate_dict_blocks(self, blobs, dictionary, caps):
+        """One raw DEFLATE stream per blob, decoded behind a dictionary (bytes for all blobs, or a list with one entry, bytes or None,
+        per blob; the last 32 KiB count): equal dictionaries are placed in the input buffer once (rcx_inflate_shared_batch)."""
+        base, off, lens, d_off, d_len, _ = _pack_shared(blobs, dictionary, 32768)
+        return self.inflate_shared(base, off, lens, d_off, d_len, caps)
+
     def inflate(self, blobs, caps):
         return self._run_host("rcx_inflate_batch", blobs, caps, extra_out=True)
 
-    def zlib_decode(self, blobs, caps, zdict=None):
+    def zlib_decode(self, blobs, caps, zdict=None, shared=False):
         """One zlib stream per blob.  zdict (bytes for all blobs, or a list with one entry, bytes or None, per blob): the preset
         dictionary of streams that carry FDICT (rcx_zlib_decode_dict_batch): its last 32 KiB are placed in front of every slot and its
-        Adler-32 must be the stream's DICTID.  None: rcx_zlib_decode_batch, which refuses FDICT."""
+        Adler-32 must be the stream's DICTID.  None: rcx_zlib_decode_batch, which refuses FDICT.  shared=True: the same results from
+        rcx_zlib_decode_shared_batch -- equal dictionaries lie in the input buffer once and nothing lies in front of the slots."""
         if zdict is None:
             return self._run_host("rcx_zlib_decode_batch", blobs, caps, extra_out=True)
+        if shared:
+            base, off, lens, d_off, d_len, dicts = _pack_shared(blobs, zdict, 32768)
+            return self._shared_decode("rcx_zlib_decode_shared_batch", base, off, lens, d_off, d_len, caps, flags=True,
+                                       dict_id=[_adler32(d) for d in dicts])
         dicts = _per_blob(zdict, len(blobs))
         return self._inflate_hist(blobs, dicts, caps, [_adler32(d) for d in dicts])
 

@@ -226,7 +226,7 @@ enum scratch_rule { SCRATCH_BY_CODEC,                                  // rcx_sc
                     SCRATCH_DEFLATE_HIST_SEGS,                         // DEFLATE levels 2..9: the real segments and the real histories
                     SCRATCH_HC_DICT_SEGS, SCRATCH_DEFLATE_DICT_SEGS,   // the real segments and the distinct dictionaries
                     SCRATCH_DC_OPTIONAL };                             // chunk states: none with contexts, and none when they cannot be had
-enum back_policy { BACK_USED_SPAN, BACK_INFLATE /* mirrored: the streams the first pass handed back */, BACK_CHAINS };
+enum back_policy { BACK_USED_SPAN, BACK_INFLATE /* mirrored: the streams the first pass handed back */, BACK_CHAINS, BACK_SLOTS /* what the blocks produced, range by range */ };
 struct codec_traits {
     bool needs_out;
     mirror_kind mirror;
@@ -256,6 +256,10 @@ static codec_traits traits_of(int codec, uint32_t param)
     case RCX_DEFLATE_ENCODE_SHARED: case RCX_ZLIB_ENCODE_SHARED: t.preload_out = true; t.scratch = SCRATCH_DEFLATE_DICT_SEGS; break;
     // the decoders with history read the bytes the caller put in front of the slots: the staged output span starts as the caller's
     case RCX_INFLATE_HIST: case RCX_ZLIB_DECODE_DICT: t.preload_out = true; break;
+    // the decoders behind shared dictionaries read theirs from the input buffer: the input span, widened by the dictionaries' ranges,
+    // travels in and nothing of the output buffer does.  They promise the caller's bytes between the slots all the same, so what the
+    // blocks produced travels back range by range (rcx_plan_slot_copies: contiguous slots are one copy), never the span across the gaps
+    case RCX_LZ4_DECODE_SHARED: case RCX_INFLATE_SHARED: case RCX_ZLIB_DECODE_SHARED: t.back = BACK_SLOTS; break;
     case RCX_DC_ENCODE: t.scratch = SCRATCH_DC_OPTIONAL; break;
     case RCX_LZ4_DECODE_LINKED: t.back = BACK_CHAINS; break;
     case RCX_ADLER32: case RCX_CRC32: case RCX_XXH32: t.needs_out = false; break;
@@ -343,6 +347,14 @@ static int launch_codec(rcx_ctx* c, const rcx_call& call, rcx_kargs& k)
     case RCX_INFLATE:
     case RCX_ZLIB_DECODE:
         rcx_tu_inflate(s, k, codec == RCX_ZLIB_DECODE, v);
+        break;
+    case RCX_LZ4_DECODE_SHARED:                                  // k.aux: the words of rcx_plan_dict, never null
+        if (!k.aux || !call.aux_in) { c->err = "lz4 decode behind shared dictionaries: use rcx_lz4_decode_shared_batch"; return RCX_RC_BAD_ARG; }
+        rcx_tu_lz4_decode_dict(s, k);
+        break;
+    case RCX_INFLATE_SHARED: case RCX_ZLIB_DECODE_SHARED:        // k.aux: the words of rcx_plan_dict, never null
+        if (!k.aux || !call.aux_in) { c->err = "inflate behind shared dictionaries: use rcx_inflate_shared_batch / rcx_zlib_decode_shared_batch"; return RCX_RC_BAD_ARG; }
+        rcx_tu_inflate_dict(s, k, codec == RCX_ZLIB_DECODE_SHARED);
         break;
     case RCX_INFLATE_HIST: case RCX_ZLIB_DECODE_DICT:            // k.aux: the history lengths (then the DICTIDs), never null
         if (!k.aux) { c->err = "inflate with history: use rcx_inflate_hist_batch / rcx_zlib_decode_dict_batch"; return RCX_RC_BAD_ARG; }
@@ -741,6 +753,10 @@ static int copy_back(rcx_ctx* c, const rcx_call& call, batch_state& st)
             for (const auto& r : rcx_plan_chain_copies(st.n, call.link->plan->head(), b->out_off, b->out_cap, st.out_len()))
                 HIPCHK(c, hipMemcpyAsync(b->out_base + r.first, st.d_out + r.first, r.second - r.first, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
+        } else if (st.t.back == BACK_SLOTS) {
+            for (const auto& r : rcx_plan_slot_copies(st.n, b->out_off, b->out_cap, st.out_len()))
+                HIPCHK(c, hipMemcpyAsync(b->out_base + r.first, st.d_out + r.first, r.second - r.first, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
         } else {
             const uint64_t used_span = rcx_plan_used_span(st.n, b->out_off, b->out_cap, st.out_len());
             if (used_span) HIPCHK(c, hipMemcpy(b->out_base, st.d_out, used_span, hipMemcpyDeviceToHost));
@@ -938,6 +954,36 @@ extern "C" int rcx_inflate_hist_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* 
 extern "C" int rcx_zlib_decode_dict_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags, const uint64_t* hist_len, const uint32_t* dict_id)
 {
     return inflate_hist_batch(c, RCX_ZLIB_DECODE_DICT, b, flags, hist_len, dict_id);
+}
+// The decoders behind SHARED DICTIONARIES: the mirror of shared_batch.  rcx_plan_dict as the encoders call it; of its words the kernels
+// read the clamped length, the offset and the DICTID (nothing is built per dictionary: no scratch), and the span of the ranges widens
+// what travels in from host memory.  The output buffer is not staged in: no slot has anything in front of it that a kernel reads.
+static int shared_decode_batch(rcx_ctx* c, int codec, const rcx_batch* b, uint32_t* flags, const uint64_t* dict_off, const uint64_t* dict_len, const uint32_t* dict_id)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    const bool lz4 = codec == RCX_LZ4_DECODE_SHARED;
+    if (!dict_off != !dict_len) { c->err = "shared dictionaries: dict_off and dict_len come together or not at all"; return RCX_RC_BAD_ARG; }
+    if (!dict_len || !b || !b->nblocks)                          // the decoders without history
+        return run_batch(c, lz4 ? call_of(RCX_LZ4_DECODE) : call_of(codec == RCX_ZLIB_DECODE_SHARED ? RCX_ZLIB_DECODE : RCX_INFLATE, 0, nullptr, flags), b);
+    if (codec == RCX_ZLIB_DECODE_SHARED && !dict_id) { c->err = "zlib decode behind shared dictionaries: null dict_id array"; return RCX_RC_BAD_ARG; }
+    rcx_dict_plan plan;
+    if (!rcx_plan_dict(b->nblocks, dict_off, dict_len, lz4 ? 65536 : 32768, lz4 ? 65535 : 32768, dict_id, lz4 ? "lz4 decode" : "inflate", plan, c->err))
+        return RCX_RC_BAD_ARG;
+    rcx_call call = call_of(codec, 0, plan.aux.data(), flags);
+    call.aux_words = RCX_DICT_WORDS; call.nhist = plan.ndict; call.dict_span = plan.span;
+    return run_batch(c, call, b);                                // (waits for the stream: the words above may go)
+}
+extern "C" int rcx_lz4_decode_shared_batch(rcx_ctx* c, const rcx_batch* b, const uint64_t* dict_off, const uint64_t* dict_len)
+{
+    return shared_decode_batch(c, RCX_LZ4_DECODE_SHARED, b, nullptr, dict_off, dict_len, nullptr);
+}
+extern "C" int rcx_inflate_shared_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags, const uint64_t* dict_off, const uint64_t* dict_len)
+{
+    return shared_decode_batch(c, RCX_INFLATE_SHARED, b, flags, dict_off, dict_len, nullptr);
+}
+extern "C" int rcx_zlib_decode_shared_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags, const uint64_t* dict_off, const uint64_t* dict_len, const uint32_t* dict_id)
+{
+    return shared_decode_batch(c, RCX_ZLIB_DECODE_SHARED, b, flags, dict_off, dict_len, dict_id);
 }
 extern "C" int rcx_bwt_forward_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_FORWARD, 0, nullptr, origin), b); }
 extern "C" int rcx_bwt_suffixes_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_SUFFIXES, 0, nullptr, origin), b); }

@@ -211,6 +211,23 @@ inline uint64_t rcx_plan_used_span(uint32_t n, const uint64_t* out_off, const ui
     }
     return used;
 }
+// what the blocks produced and nothing else: block i's first min(out_len, out_cap) bytes at out_off[i], blocks that touch (in batch order)
+// as one range.  [first, second) byte ranges in batch order.  For the calls that promise the caller's bytes BETWEEN the slots without
+// staging the output buffer in (the decoders behind shared dictionaries): contiguous slots travel as one copy, slots with gaps one each.
+inline std::vector<std::pair<uint64_t, uint64_t>> rcx_plan_slot_copies(uint32_t n, const uint64_t* out_off, const uint64_t* out_cap, const uint64_t* out_len)
+{
+    std::vector<std::pair<uint64_t, uint64_t>> r;
+    uint64_t lo = 0, hi = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t l = out_len[i] < out_cap[i] ? out_len[i] : out_cap[i];
+        if (!l) continue;
+        if (hi > lo && out_off[i] == hi) { hi += l; continue; }
+        if (hi > lo) r.emplace_back(lo, hi);
+        lo = out_off[i]; hi = lo + l;
+    }
+    if (hi > lo) r.emplace_back(lo, hi);
+    return r;
+}
 // a chain's bytes lie behind its head's out_off, as many as its blocks' out_len add up to (its head's out_cap at the most); chains
 // that touch travel as one copy.  [first, second) byte ranges in chain order.
 inline std::vector<std::pair<uint64_t, uint64_t>> rcx_plan_chain_copies(uint32_t n, const uint32_t* head, const uint64_t* out_off,

@@ -17,6 +17,8 @@ uint64_t rcx_tu_lz4_encode_scratch(uint32_t nblocks);
 void rcx_tu_inflate(hipStream_t s, rcx_kargs& k, bool zlib, int variant);
 // ... with history (k_inflate_hist.hip): k.aux = n history lengths (uint32), then n DICTIDs (zlib); flags come back in the first n
 void rcx_tu_inflate_hist(hipStream_t s, rcx_kargs& k, bool zlib);
+// ... behind shared dictionaries (k_inflate_dict.hip): k.aux = the words of rcx_plan_dict; flags come back in the first n
+void rcx_tu_inflate_dict(hipStream_t s, rcx_kargs& k, bool zlib);
 void rcx_tu_adler32(hipStream_t s, rcx_kargs& k);
 void rcx_tu_crc32(hipStream_t s, rcx_kargs& k);
 void rcx_tu_gzip_decode(hipStream_t s, rcx_kargs& k, int variant);
@@ -63,3 +65,5 @@ void rcx_tu_xxh32(hipStream_t s, rcx_kargs& k, uint32_t seed);
 // head; dict[i]: a head's dictionary bytes; eff[i] (written): where block i's output starts in out_base.  Device arrays.
 void rcx_tu_lz4_decode_linked(hipStream_t s, rcx_kargs& k, const uint32_t* order, const uint32_t* rounds_off, uint32_t nrounds,
                               const uint32_t* head, const uint32_t* dict, uint64_t* eff);
+// LZ4 block decode behind shared dictionaries (k_lz4_dict.hip), one wave per block: k.aux = the words of rcx_plan_dict
+void rcx_tu_lz4_decode_dict(hipStream_t s, rcx_kargs& k);

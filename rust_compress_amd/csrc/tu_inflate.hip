@@ -5,12 +5,14 @@
 #include "k_inflate.hip"
 #include "k_inflate2.hip"
 #include "k_inflate_hist.hip"          // with history, on k_inflate2.hip's machinery
+#include "k_inflate_dict.hip"          // behind shared dictionaries, likewise
 #include "k_inflate3.hip"
 #include "k_crc32.hip"
 #include "k_gzip.hip"
 
 void rcx_tu_inflate(hipStream_t s, rcx_kargs& k, bool zlib, int variant) { launch_inflate(s, k, zlib, variant); }
 void rcx_tu_inflate_hist(hipStream_t s, rcx_kargs& k, bool zlib) { launch_inflate_hist(s, k, zlib); }
+void rcx_tu_inflate_dict(hipStream_t s, rcx_kargs& k, bool zlib) { launch_inflate_dict(s, k, zlib); }
 void rcx_tu_adler32(hipStream_t s, rcx_kargs& k) { launch_adler32(s, k); }
 void rcx_tu_crc32(hipStream_t s, rcx_kargs& k) { launch_crc32(s, k); }
 void rcx_tu_gzip_decode(hipStream_t s, rcx_kargs& k, int variant) { launch_gzip_decode(s, k, variant); }
