@@ -446,6 +446,33 @@ int rcx_rle_encode_batch(rcx_ctx*, const rcx_batch*);
 int rcx_rle_decode_batch(rcx_ctx*, const rcx_batch*);
 uint64_t rcx_rle_encode_bound(uint64_t in_len);
 
+/* ---- dictionary training (extension: the reference has no trainer) ------------------------------------------------------------
+ * Makes the dictionaries the calls with history and behind shared dictionaries take as given: for each of many independent corpora
+ * it selects the segments that cover the most frequent substrings -- COVER (Liao, Petri, Moffat, Wirth 2016) in the hashed form zstd
+ * calls "fastcover" -- and writes a RAW-CONTENT dictionary, what LZ4 and zlib take.  Block i of the batch is job i: in_off / in_len the
+ * corpus, the concatenation of nsamples[i] samples whose lengths are the next nsamples[i] entries of the flat host array sample_len
+ * (job order; lengths of 0 are allowed); out_off / out_cap the dictionary's slot and its capacity C.  d is the length of the hashed
+ * substrings (6 or 8), k the length of a segment (d .. 4096), f the log2 of the frequency table (10 .. 22).
+ *   contract   the bytes are DEFINED by the specification in DESIGN.md 3.19 (epochs of max(1, C / k / 4), the start with the greatest
+ *              sum of the frequencies of its segment's DISTINCT hashes, ties to the lowest start, trimmed, its frequencies zeroed,
+ *              copied to the dictionary's end first; ten rounds in a row without a start end the job) and equal the serial reference of
+ *              tests/dict_train_ref byte for byte.  The dictionary is delivered at the slot's START: out_len[i] <= C, in_used[i] =
+ *              in_len[i], status RCX_OK.  A corpus shorter than k, a capacity below d or a corpus without a whole substring give
+ *              out_len 0 with RCX_OK.  Slot bytes beyond out_len are unspecified; nothing outside the slots is written.  The result
+ *              depends on the corpus, the sample lengths, k, d, f and C alone: not on the job's place, its neighbours or `mem`.
+ *   limits     at most 65535 jobs a call; a corpus and a capacity below 4 GiB.  RCX_RC_BAD_ARG, with the job named by
+ *              rcx_last_error: sample lengths that do not add up to in_len[i], in_len[i] >= 2^32, d other than 6 or 8, k or f out of
+ *              range, a null array.  nblocks == 0 is RCX_RC_OK.
+ *   scratch    rcx_dict_train_scratch_bytes(njobs, max_corpus, max_cap, k, f): per job 10 bytes per corpus byte (hash words, distances,
+ *              score differences) + 4 << f for the frequencies + C; the batch call allocates what the real sizes take in the context.
+ *   cost       one pass to hash and count, one to find every position's previous occurrence (k - d LDS reads a position), then four
+ *              launches a ROUND for all live jobs together, each O(epoch), about C / k rounds and a few; the call is synchronous and
+ *              reads one word back every eight rounds to stop when every job is done.  Measurements: DESIGN.md 3.19.
+ *   not here   zstd's dictionary header and entropy tables; a search over k and d (batch the parameter sets as separate calls);
+ *              rcx_launch_dev, which does not take RCX_DICT_TRAIN, as it takes none of the *_SHARED ids. */
+int rcx_dict_train_batch(rcx_ctx*, const rcx_batch*, const uint32_t* nsamples, const uint64_t* sample_len, uint32_t k, uint32_t d, uint32_t f);
+uint64_t rcx_dict_train_scratch_bytes(uint32_t njobs, uint64_t max_corpus, uint64_t max_cap, uint32_t k, uint32_t f);
+
 /* ---- device-resident descriptors (benchmark / pipeline use) ------------------ */
 /* Same kernels, but every array (offsets, lengths, status, ...) already lives
  * in HBM, nothing is copied and nothing is synchronised: the call enqueues on
@@ -483,7 +510,8 @@ enum rcx_codec {
 enum rcx_xcodec { RCX_XXH32 = 32, RCX_LZ4_DECODE_LINKED = 33, RCX_LZ4_ENCODE_HIST = 34, RCX_DEFLATE_ENCODE_HIST = 35, RCX_ZLIB_ENCODE_DICT = 36,
                   RCX_INFLATE_HIST = 37, RCX_ZLIB_DECODE_DICT = 38, RCX_LZ4_ENCODE_SHARED = 39, RCX_DEFLATE_ENCODE_SHARED = 40,
                   RCX_ZLIB_ENCODE_SHARED = 41, RCX_LZ4_DECODE_SHARED = 42, RCX_INFLATE_SHARED = 43, RCX_ZLIB_DECODE_SHARED = 44,
-                  RCX_XCODEC_END = 45 };
+                  RCX_DICT_TRAIN = 45,
+                  RCX_XCODEC_END = 46 };
 /* scratch bytes (HBM) the codec needs for nblocks blocks of <= max_block bytes.  Required for LZ4 encode, BWT and gzip
  * decode and the DEFLATE / zlib / gzip encoders; for RCX_INFLATE / RCX_ZLIB_DECODE it is what the default (wave-per-stream) decoder needs -- without it
  * rcx_launch_dev falls back to the lane-per-stream kernel (same results, slower on small batches). */

@@ -131,7 +131,8 @@ pub const RCX_ZLIB_ENCODE_SHARED: c_int = 41;
 pub const RCX_LZ4_DECODE_SHARED: c_int = 42;
 pub const RCX_INFLATE_SHARED: c_int = 43;
 pub const RCX_ZLIB_DECODE_SHARED: c_int = 44;
-pub const RCX_XCODEC_END: c_int = 45;
+pub const RCX_DICT_TRAIN: c_int = 45;
+pub const RCX_XCODEC_END: c_int = 46;
 
 #[link(name = "rcx")]
 extern "C" {
@@ -186,6 +187,9 @@ extern "C" {
     pub fn rcx_lz4_decode_shared_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, dict_off: *const u64, dict_len: *const u64) -> c_int;
     pub fn rcx_inflate_shared_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32, dict_off: *const u64, dict_len: *const u64) -> c_int;
     pub fn rcx_zlib_decode_shared_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, flags: *mut u32, dict_off: *const u64, dict_len: *const u64, dict_id: *const u32) -> c_int;
+    // ---- dictionary training (extension): raw-content dictionaries for the calls above, one job per block
+    pub fn rcx_dict_train_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, nsamples: *const u32, sample_len: *const u64, k: u32, d: u32, f: u32) -> c_int;
+    pub fn rcx_dict_train_scratch_bytes(njobs: u32, max_corpus: u64, max_cap: u64, k: u32, f: u32) -> u64;
     // ---- BWT / MTF / DC (src/bwt/mod.rs, mtf.rs, dc.rs)
     pub fn rcx_bwt_forward_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;
     pub fn rcx_bwt_suffixes_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;

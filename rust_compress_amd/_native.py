@@ -52,6 +52,7 @@ EXPORTS = [
     "rcx_lz4_encode_hc_shared_batch", "rcx_deflate_encode_shared_batch", "rcx_zlib_encode_shared_batch",
     "rcx_lz4_hc_shared_scratch_bytes", "rcx_deflate_shared_scratch_bytes",
     "rcx_lz4_decode_shared_batch", "rcx_inflate_shared_batch", "rcx_zlib_decode_shared_batch",
+    "rcx_dict_train_batch", "rcx_dict_train_scratch_bytes",
 ]
 
 
@@ -138,6 +139,9 @@ def lib():
         for name in ("rcx_lz4_hc_shared_scratch_bytes", "rcx_deflate_shared_scratch_bytes"):
             getattr(L, name).argtypes = [C.c_uint32, C.c_uint64, C.c_uint32]
             getattr(L, name).restype = C.c_uint64
+        L.rcx_dict_train_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.rcx_dict_train_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
+        L.rcx_dict_train_scratch_bytes.restype = C.c_uint64
         L.rcx_deflate_level_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64]
         L.rcx_deflate_level_scratch_bytes.restype = C.c_uint64
         for name in ("rcx_inflate_batch", "rcx_zlib_decode_batch", "rcx_adler32_batch", "rcx_crc32_batch",

@@ -320,6 +320,35 @@ class Context:
         base, off, lens, d_off, d_len, _ = _pack_shared(blobs, dictionary, 32768)
         return self.inflate_shared(base, off, lens, d_off, d_len, caps)
 
+    def train_dictionaries(self, corpora, sizes, k=256, d=8, f=20):
+        """One raw-content dictionary per corpus (rcx_dict_train_batch): corpora is a list of lists of samples (bytes), sizes the
+        dictionaries' capacities.  For every corpus the segments of k bytes that cover the most frequent d-byte substrings (d = 6 or 8,
+        hashed into 2^f counters) are selected, the most valuable last; a dictionary may come out shorter than its capacity, or empty
+        for a corpus shorter than k.  -> list of bytes, to be handed as they are to lz4_encode_hc_dict_blocks,
+        deflate_encode_dict_blocks, zlib_encode(..., zdict=, shared=True) and their decoders."""
+        n = len(corpora)
+        if len(sizes) != n:
+            raise ValueError("sizes: one entry per corpus")
+        base, off, lens = B.pack([b"".join(bytes(s) for s in c) for c in corpora])
+        nsamples = np.array([len(c) for c in corpora] or [0], np.uint32)
+        sample_len = np.array([len(s) for c in corpora for s in c] or [0], np.uint64)
+        total, ooff, ocap = B.layout([int(x) for x in sizes])
+        out = np.zeros(total, dtype=np.uint8)
+        out_len = np.zeros(max(n, 1), np.uint64)
+        in_used = np.zeros(max(n, 1), np.uint64)
+        status = np.zeros(max(n, 1), np.int32)
+        if not n:
+            off = lens = ooff = ocap = np.zeros(1, np.uint64)
+        p = lambda a: a.ctypes.data
+        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
+        self._chk(N.lib().rcx_dict_train_batch(self._h, C.byref(b), C.c_void_p(p(nsamples)), C.c_void_p(p(sample_len)), int(k), int(d), int(f)))
+        Result([], out_len[:n], in_used[:n], status[:n], None).check()
+        return B.unpack(out, ooff, out_len[:n])
+
+    def train_dictionary(self, samples, size, k=256, d=8, f=20):
+        """train_dictionaries for one corpus -> bytes"""
+        return self.train_dictionaries([samples], [size], k, d, f)[0]
+
     def inflate(self, blobs, caps):
         return self._run_host("rcx_inflate_batch", blobs, caps, extra_out=True)
 

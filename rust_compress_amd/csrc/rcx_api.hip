@@ -215,6 +215,7 @@ struct rcx_call {
     uint32_t nhist;                      // LZ4 HC / DEFLATE encode with history: the blocks that have one (their lengths are aux_in); behind shared dictionaries: the distinct dictionaries
     uint32_t aux_words;                  // words per block of aux_in: 1, or 2 (the zlib calls with history: lengths, then DICTIDs), or RCX_DICT_WORDS
     uint64_t dict_span;                  // shared dictionaries: one past their highest byte in the input buffer (it travels in with the blocks)
+    const rcx_train_plan* train;         // dictionary training: the plan of the call (its words are aux_in), else null
 };
 
 // ---- per-codec traits of the host path ------------------------------------------------------------------------------------------------
@@ -225,6 +226,7 @@ enum scratch_rule { SCRATCH_BY_CODEC,                                  // rcx_sc
                     SCRATCH_HC_HIST_SEGS,                              // ... and the chains of the real histories
                     SCRATCH_DEFLATE_HIST_SEGS,                         // DEFLATE levels 2..9: the real segments and the real histories
                     SCRATCH_HC_DICT_SEGS, SCRATCH_DEFLATE_DICT_SEGS,   // the real segments and the distinct dictionaries
+                    SCRATCH_TRAIN,                                     // dictionary training: what the call's plan carved
                     SCRATCH_DC_OPTIONAL };                             // chunk states: none with contexts, and none when they cannot be had
 enum back_policy { BACK_USED_SPAN, BACK_INFLATE /* mirrored: the streams the first pass handed back */, BACK_CHAINS, BACK_SLOTS /* what the blocks produced, range by range */ };
 struct codec_traits {
@@ -260,6 +262,9 @@ static codec_traits traits_of(int codec, uint32_t param)
     // travels in and nothing of the output buffer does.  They promise the caller's bytes between the slots all the same, so what the
     // blocks produced travels back range by range (rcx_plan_slot_copies: contiguous slots are one copy), never the span across the gaps
     case RCX_LZ4_DECODE_SHARED: case RCX_INFLATE_SHARED: case RCX_ZLIB_DECODE_SHARED: t.back = BACK_SLOTS; break;
+    // dictionary training writes a slot's first out_len bytes and promises the rest of the caller's buffer: nothing of the output travels
+    // in, and what the jobs produced travels back slot by slot
+    case RCX_DICT_TRAIN: t.back = BACK_SLOTS; t.scratch = SCRATCH_TRAIN; break;
     case RCX_DC_ENCODE: t.scratch = SCRATCH_DC_OPTIONAL; break;
     case RCX_LZ4_DECODE_LINKED: t.back = BACK_CHAINS; break;
     case RCX_ADLER32: case RCX_CRC32: case RCX_XXH32: t.needs_out = false; break;
@@ -269,7 +274,7 @@ static codec_traits traits_of(int codec, uint32_t param)
 }
 static rcx_call call_of(int codec, uint32_t param = 0, const uint32_t* aux_in = nullptr, uint32_t* aux_out = nullptr, const uint64_t* n_out = nullptr)
 {
-    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr, 0, 1, 0};
+    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr, 0, 1, 0, nullptr};
 }
 
 // ---- kernel arguments: built here and nowhere else ---------------------------------------------------------------------------------------
@@ -356,6 +361,11 @@ static int launch_codec(rcx_ctx* c, const rcx_call& call, rcx_kargs& k)
         if (!k.aux || !call.aux_in) { c->err = "inflate behind shared dictionaries: use rcx_inflate_shared_batch / rcx_zlib_decode_shared_batch"; return RCX_RC_BAD_ARG; }
         rcx_tu_inflate_dict(s, k, codec == RCX_ZLIB_DECODE_SHARED);
         break;
+    case RCX_DICT_TRAIN: {                                       // k.aux: the words of rcx_plan_train; returns when the last round has run
+        if (!call.train || !k.aux) { c->err = "dict train: use rcx_dict_train_batch"; return RCX_RC_BAD_ARG; }
+        int rc = rcx_tu_dict_train(s, k, *call.train, c->err);
+        if (rc) return rc;
+        break; }
     case RCX_INFLATE_HIST: case RCX_ZLIB_DECODE_DICT:            // k.aux: the history lengths (then the DICTIDs), never null
         if (!k.aux) { c->err = "inflate with history: use rcx_inflate_hist_batch / rcx_zlib_decode_dict_batch"; return RCX_RC_BAD_ARG; }
         rcx_tu_inflate_hist(s, k, codec == RCX_ZLIB_DECODE_DICT);
@@ -599,6 +609,7 @@ static int reserve_scratch(rcx_ctx* c, const rcx_call& call, batch_state& st)
         for (uint32_t i = 0; i < n; i++) segs += rcx_tu_deflate_encode_segments(b->in_len[i]);
         sb = rcx_tu_deflate_dict_scratch(n, segs, call.nhist);
         break;
+    case SCRATCH_TRAIN: sb = call.train ? call.train->scratch_bytes : 0; break;
     case SCRATCH_DC_OPTIONAL:                                       // withctx: the wave-per-block kernel encodes, no chunk states
         sb = call.param ? 0 : rcx_scratch_bytes(call.codec, n, st.sp.max_block);
         break;
@@ -984,6 +995,23 @@ extern "C" int rcx_inflate_shared_batch(rcx_ctx* c, const rcx_batch* b, uint32_t
 extern "C" int rcx_zlib_decode_shared_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* flags, const uint64_t* dict_off, const uint64_t* dict_len, const uint32_t* dict_id)
 {
     return shared_decode_batch(c, RCX_ZLIB_DECODE_SHARED, b, flags, dict_off, dict_len, dict_id);
+}
+// DICTIONARY TRAINING: job i is block i.  rcx_plan_train checks the arguments, does the epoch arithmetic and carves the scratch; its words
+// (the jobs' headers and the sample ends) go to the kernels in the descriptors' aux array, as many words per job as they take.
+extern "C" int rcx_dict_train_batch(rcx_ctx* c, const rcx_batch* b, const uint32_t* nsamples, const uint64_t* sample_len, uint32_t k, uint32_t d, uint32_t f)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    rcx_call call = call_of(RCX_DICT_TRAIN);
+    rcx_train_plan plan;
+    if (!b) { c->err = "null descriptor array"; return RCX_RC_BAD_ARG; }
+    if (!rcx_plan_train(b->nblocks, b->in_len, b->out_cap, nsamples, sample_len, k, d, f, plan, c->err)) return RCX_RC_BAD_ARG;
+    if (!b->nblocks) return RCX_RC_OK;
+    call.aux_in = plan.aux.data(); call.aux_words = plan.aux_words; call.train = &plan;
+    return run_batch(c, call, b);                                // (waits for the stream: the plan above may go)
+}
+extern "C" uint64_t rcx_dict_train_scratch_bytes(uint32_t njobs, uint64_t max_corpus, uint64_t max_cap, uint32_t k, uint32_t f)
+{
+    return rcx_plan_train_scratch(njobs, max_corpus, max_cap, k, f);
 }
 extern "C" int rcx_bwt_forward_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_FORWARD, 0, nullptr, origin), b); }
 extern "C" int rcx_bwt_suffixes_batch(rcx_ctx* c, const rcx_batch* b, uint32_t* origin) { return run_batch(c, call_of(RCX_BWT_SUFFIXES, 0, nullptr, origin), b); }

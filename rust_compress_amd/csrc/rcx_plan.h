@@ -251,3 +251,118 @@ inline std::vector<std::pair<uint64_t, uint64_t>> rcx_plan_chain_copies(uint32_t
     if (hi > lo) r.emplace_back(lo, hi);
     return r;
 }
+
+// ---- dictionary training (rcx_dict_train_batch, k_dict_train.hip) -------------------------------------------------------------------
+// Job i trains one dictionary of out_cap[i] bytes from the corpus in_len[i], the concatenation of nsamples[i] samples.  The plan checks
+// the arguments, does the epoch arithmetic of DESIGN.md 3.19, bounds the rounds and lays out the scratch; its words go to the kernels
+// in the descriptors' aux array:
+//   [0, N)                          comes back: the rounds job i ran
+//   [N + RCX_TRAIN_HDR * i ...)     job i: first sample end (index), samples, E, size, scratch offset (low, high), dead, 0
+//   [N * (1 + RCX_TRAIN_HDR) ...)   the sample ENDS of every job (prefix sums of its lengths, 32 bits: a corpus is shorter than 4 GiB)
+// The carve below is constexpr so that the kernels compute a job's arrays from the same function.
+#define RCX_TRAIN_PASSES 4u
+#define RCX_TRAIN_ZERO_RUNS 10u
+#define RCX_TRAIN_HDR 8u
+#define RCX_TRAIN_SCAN_BLOCKS 128u            /* workgroups a job in the two scan launches: one partial sum each */
+#define RCX_TRAIN_STATE_WORDS 16u             /* tail, zero, done, rounds, best (64 bits), padding */
+#define RCX_TRAIN_MAX_JOBS 65535u             /* the job index rides on a grid dimension */
+constexpr uint64_t rcx_train_up(uint64_t x) { return (x + 255u) & ~(uint64_t)255u; }
+struct rcx_train_carve { uint64_t hash, back, freq, diff, stage, end; };      // byte offsets inside a job's region
+// hash: a word per position; back: 16 bits per position; freq: 2^f words; diff: size + 1 words; stage: the dictionary, built from its end
+constexpr rcx_train_carve rcx_train_job_carve(uint64_t n, uint64_t cap, uint64_t size, uint32_t f)
+{
+    rcx_train_carve c = {0, 0, 0, 0, 0, 0};
+    c.back = c.hash + rcx_train_up(4 * n);
+    c.freq = c.back + rcx_train_up(2 * n);
+    c.diff = c.freq + rcx_train_up((uint64_t)4 << f);
+    c.stage = c.diff + rcx_train_up(4 * (size + 1));
+    c.end = c.stage + rcx_train_up(cap);
+    return c;
+}
+// in front of the jobs' regions: 256 bytes of counters (word 0: the jobs that are done), the jobs' state, the scan's partial sums
+constexpr uint64_t rcx_train_state_at(uint32_t) { return 256; }
+constexpr uint64_t rcx_train_partial_at(uint32_t njobs) { return 256 + rcx_train_up((uint64_t)njobs * RCX_TRAIN_STATE_WORDS * 4); }
+constexpr uint64_t rcx_train_head_bytes(uint32_t njobs) { return rcx_train_partial_at(njobs) + rcx_train_up((uint64_t)njobs * RCX_TRAIN_SCAN_BLOCKS * 4); }
+struct rcx_train_epochs { uint64_t E, size; };
+// E = max(1, C / k / PASSES), size = n / E; epochs shorter than 10 k are made 10 k long (or n), and E follows
+constexpr rcx_train_epochs rcx_train_epoch_plan(uint64_t n, uint64_t cap, uint32_t k)
+{
+    rcx_train_epochs e = {cap / k / RCX_TRAIN_PASSES, 0};
+    if (e.E < 1) e.E = 1;
+    e.size = n / e.E;
+    if (e.size < (uint64_t)10 * k) {
+        e.size = (uint64_t)10 * k < n ? (uint64_t)10 * k : n;
+        e.E = e.size ? n / e.size : 1;
+        if (e.E < 1) e.E = 1;
+    }
+    return e;
+}
+// a job that cannot produce a byte (n < k: no start; C < d: no segment fits) runs no round and has no region
+constexpr bool rcx_train_dead(uint64_t n, uint64_t cap, uint32_t k, uint32_t d) { return n < k || cap < d; }
+// every round that picks a start takes d bytes or more off the tail or ends the job, and fewer than ZERO_RUNS rounds in a row pick none
+constexpr uint64_t rcx_train_round_bound(uint64_t cap, uint32_t d) { return (cap / d + 2) * (RCX_TRAIN_ZERO_RUNS + 1); }
+struct rcx_train_plan {
+    std::vector<uint32_t> aux;
+    uint32_t aux_words = 1;                      // words per job of aux (run_batch stages aux_words * n)
+    uint32_t k = 0, d = 0, f = 0;
+    uint64_t scratch_bytes = 0;                  // with 256 bytes of slack: the kernels align the base
+    uint64_t max_rounds = 0, max_n = 0, max_size = 0, max_cap = 0;
+    uint32_t live = 0;                           // jobs that run rounds
+};
+// false: `err` names the job
+inline bool rcx_plan_train(uint32_t n, const uint64_t* in_len, const uint64_t* out_cap, const uint32_t* nsamples, const uint64_t* sample_len,
+                           uint32_t k, uint32_t d, uint32_t f, rcx_train_plan& p, std::string& err)
+{
+    p = rcx_train_plan();
+    p.k = k; p.d = d; p.f = f;
+    if (d != 6 && d != 8) { err = "dict train: d must be 6 or 8"; return false; }
+    if (k < d || k > 4096) { err = "dict train: k must be d..4096"; return false; }
+    if (f < 10 || f > 22) { err = "dict train: f must be 10..22"; return false; }
+    if (n > RCX_TRAIN_MAX_JOBS) { err = "dict train: at most 65535 jobs a call"; return false; }
+    if (n && (!in_len || !out_cap || !nsamples)) { err = "dict train: null array"; return false; }
+    const size_t N = n;
+    uint64_t total = 0;
+    for (size_t i = 0; i < N; i++) total += nsamples[i];
+    if (total && !sample_len) { err = "dict train: null sample_len array"; return false; }
+    const uint64_t words = (uint64_t)N * (1 + RCX_TRAIN_HDR) + total;
+    p.aux_words = N ? (uint32_t)((words + N - 1) / N) : 1;
+    p.aux.assign((size_t)p.aux_words * N, 0);
+    uint64_t at = rcx_train_head_bytes(n), first = 0;
+    for (size_t i = 0; i < N; i++) {
+        if (in_len[i] >> 32 || out_cap[i] >> 32) {
+            err = "dict train: job " + std::to_string(i) + ": a corpus or a capacity of 4 GiB or more";
+            return false;
+        }
+        uint64_t sum = 0;
+        uint32_t* ends = p.aux.data() + N * (1 + RCX_TRAIN_HDR) + first;
+        for (uint32_t s = 0; s < nsamples[i]; s++) {
+            const uint64_t l = sample_len[first + s];
+            if (l > in_len[i] - sum) { sum = ~(uint64_t)0; break; }
+            sum += l;
+            ends[s] = (uint32_t)sum;
+        }
+        if (sum != in_len[i]) {
+            err = "dict train: job " + std::to_string(i) + ": the sample lengths do not add up to in_len " + std::to_string(in_len[i]);
+            return false;
+        }
+        const rcx_train_epochs e = rcx_train_epoch_plan(in_len[i], out_cap[i], k);
+        const bool dead = rcx_train_dead(in_len[i], out_cap[i], k, d);
+        uint32_t* h = p.aux.data() + N + RCX_TRAIN_HDR * i;
+        h[0] = (uint32_t)first; h[1] = nsamples[i]; h[2] = (uint32_t)e.E; h[3] = (uint32_t)e.size;
+        h[4] = (uint32_t)at; h[5] = (uint32_t)(at >> 32); h[6] = dead ? 1u : 0u;
+        first += nsamples[i];
+        if (dead) continue;
+        at += rcx_train_job_carve(in_len[i], out_cap[i], e.size, f).end;
+        p.live++;
+        p.max_rounds = std::max(p.max_rounds, rcx_train_round_bound(out_cap[i], d));
+        p.max_n = std::max(p.max_n, in_len[i]); p.max_size = std::max(p.max_size, e.size); p.max_cap = std::max(p.max_cap, out_cap[i]);
+    }
+    p.scratch_bytes = at + 256;
+    return true;
+}
+// every job counted at max_corpus and max_cap, and its epoch at the whole corpus (a small capacity makes one epoch of it)
+inline uint64_t rcx_plan_train_scratch(uint32_t njobs, uint64_t max_corpus, uint64_t max_cap, uint32_t k, uint32_t f)
+{
+    if (f < 10 || f > 22 || k < 6 || k > 4096) return 0;
+    return rcx_train_head_bytes(njobs) + (uint64_t)njobs * rcx_train_job_carve(max_corpus, max_cap, max_corpus, f).end + 256;
+}

@@ -67,3 +67,7 @@ void rcx_tu_lz4_decode_linked(hipStream_t s, rcx_kargs& k, const uint32_t* order
                               const uint32_t* head, const uint32_t* dict, uint64_t* eff);
 // LZ4 block decode behind shared dictionaries (k_lz4_dict.hip), one wave per block: k.aux = the words of rcx_plan_dict
 void rcx_tu_lz4_decode_dict(hipStream_t s, rcx_kargs& k);
+// tu_dict_train.hip: the batched dictionary trainer (k_dict_train.hip): k.aux = the words of rcx_plan_train; synchronous (it reads a
+// count of finished jobs back every few rounds)
+struct rcx_train_plan;
+int rcx_tu_dict_train(hipStream_t s, rcx_kargs& k, const rcx_train_plan& plan, std::string& err);
