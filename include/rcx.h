@@ -84,7 +84,13 @@ enum rcx_status {
     /* a limit of this implementation, not of the format: bwt::Encoder::new(w, block_size) takes any usize (bwt/mod.rs:451), the suffix
      * sorter keeps four flag bits beside a suffix index -- a block of 2^28 bytes or more gets this status (out_len 0) and the rest of
      * the batch is transformed.  The host mirrors turn it into io::ErrorKind::InvalidInput. */
-    RCX_E_BWT_BLOCK_TOO_LARGE = 60  /* "bwt block of 2^28 bytes or more" */
+    RCX_E_BWT_BLOCK_TOO_LARGE = 60, /* "bwt block of 2^28 bytes or more" */
+    /* bzip2 files (extension, see rcx_bzip2_decode_batch) */
+    RCX_E_BZ2_MAGIC = 70,           /* the first 4 bytes are not BZh1..BZh9 */
+    RCX_E_BZ2_DATA = 71,            /* a malformed block or stream structure */
+    RCX_E_BZ2_BLOCK_CRC = 72,       /* a block's CRC does not match */
+    RCX_E_BZ2_STREAM_CRC = 73,      /* a stream's combined CRC does not match */
+    RCX_E_BZ2_RANDOMISED = 74       /* the obsolete randomised bit is set (bzip2 has not written it since 0.9.5): not supported */
 };
 
 /* ---- batch-level return codes --------------------------------------------- */
@@ -473,6 +479,34 @@ uint64_t rcx_rle_encode_bound(uint64_t in_len);
 int rcx_dict_train_batch(rcx_ctx*, const rcx_batch*, const uint32_t* nsamples, const uint64_t* sample_len, uint32_t k, uint32_t d, uint32_t f);
 uint64_t rcx_dict_train_scratch_bytes(uint32_t njobs, uint64_t max_corpus, uint64_t max_cap, uint32_t k, uint32_t f);
 
+/* ---- bzip2 (extension: the reference's block-sorting container is its own bwt | mtf/dc | ari pipeline, which no other tool reads) ----
+ * DECODE of .bz2 files as bzip2 / libbz2 write them.  Block i of the batch is one whole FILE: one or more concatenated streams, optionally
+ * followed by other bytes; its decoded bytes go to its output slot.
+ *   results    success: RCX_OK, out_len[i] = the decoded size, in_used[i] = the byte just after the last accepted stream's padding (a
+ *              following stream is one whose first 4 bytes are BZh1..BZh9, and its errors count; anything else ends the file with RCX_OK).
+ *              The file decodes but out_cap[i] is too small: RCX_E_OUTPUT_TOO_SMALL and out_len[i] = the exact size needed -- every
+ *              block and stream CRC has been checked by then, one retry suffices, and out_cap = 0 is a size query.  Any other failure:
+ *              the first failure in stream order, out_len 0, in_used 0.  RCX_E_EOF: the input ends inside a stream (also a file
+ *              shorter than 4 bytes).  RCX_E_BZ2_DATA: everything the format calls an error that has no status of its own, among
+ *              them more than 18002 selectors.  Nothing outside a file's own slot is written, a failing file affects no other, and
+ *              a slot is written only up to the blocks that had passed their CRC when the failure was found.
+ *   oracle     bytes, out_len, in_used and accept / reject are libbz2's, with two exceptions: randomised blocks, which libbz2 still
+ *              reads, are refused (RCX_E_BZ2_RANDOMISED); and a crafted block whose L is the BWT of nothing, with a cycle through
+ *              origPtr that does not divide the block's length, is RCX_E_BZ2_BLOCK_CRC here where libbz2, which walks the cycle the
+ *              other way round, accepts it when the CRC is that of its own walk (no encoder writes such a block).
+ *   limits     a file and a slot below 4 GiB; at most 65535 files a call (more: RCX_RC_BAD_ARG).  Decode only.
+ *   knob       rcx_ctx_set_param(ctx, RCX_BZIP2_DECODE, r): block candidates a round, 64..4096; 0 (the default) is 1536.  The one
+ *              parameter of an extension id, and this call reads it.
+ *   stages     a scan of every bit position for the two 48-bit marks and of every byte position for BZh1..9; one wave per block mark
+ *              decodes speculatively (Huffman, selectors, MTF, RUNA/RUNB) into scratch; the host chains the candidates into streams
+ *              (rcx_plan_bz2_chain) and drops the marks that occurred inside data; rcx_bwt_inverse_minimal_batch's kernel on the live
+ *              blocks; the run-length step undone and the CRCs computed wave-parallel.  Candidates go in rounds of 1536, so
+ *              the scratch (the context's: about 2.1 x 100 000 x the files' highest level bytes a candidate of a round -- 2.9 GB for a
+ *              full round at level 9 -- and up to 2 GiB for the inverse BWT of large blocks) does not grow with the file.  The call is
+ *              synchronous and reads counts back between the stages.  DESIGN.md 3.20 has the kernels and measurements.
+ *   not here   rcx_launch_dev and rcx_multi_batch, which do not take RCX_BZIP2_DECODE. */
+int rcx_bzip2_decode_batch(rcx_ctx*, const rcx_batch*);
+
 /* ---- device-resident descriptors (benchmark / pipeline use) ------------------ */
 /* Same kernels, but every array (offsets, lengths, status, ...) already lives
  * in HBM, nothing is copied and nothing is synchronised: the call enqueues on
@@ -506,12 +540,13 @@ enum rcx_codec {
     RCX_DEFLATE_ENCODE, RCX_ZLIB_ENCODE, RCX_GZIP_ENCODE, RCX_CODEC_COUNT
 };
 /* Ids of the batch entry points that rcx_launch_dev, rcx_multi_* and rcx_scratch_bytes do not take (enum rcx_codec stays as it is for
- * those): they name the entry point to rcx_ctx_set_variant / rcx_ctx_set_param, neither of which has a setting for them yet. */
+ * those): they name the entry point to rcx_ctx_set_variant / rcx_ctx_set_param, neither of which has a setting for them yet, but for
+ * RCX_BZIP2_DECODE's parameter (the candidates a round, see rcx_bzip2_decode_batch). */
 enum rcx_xcodec { RCX_XXH32 = 32, RCX_LZ4_DECODE_LINKED = 33, RCX_LZ4_ENCODE_HIST = 34, RCX_DEFLATE_ENCODE_HIST = 35, RCX_ZLIB_ENCODE_DICT = 36,
                   RCX_INFLATE_HIST = 37, RCX_ZLIB_DECODE_DICT = 38, RCX_LZ4_ENCODE_SHARED = 39, RCX_DEFLATE_ENCODE_SHARED = 40,
                   RCX_ZLIB_ENCODE_SHARED = 41, RCX_LZ4_DECODE_SHARED = 42, RCX_INFLATE_SHARED = 43, RCX_ZLIB_DECODE_SHARED = 44,
-                  RCX_DICT_TRAIN = 45,
-                  RCX_XCODEC_END = 46 };
+                  RCX_DICT_TRAIN = 45, RCX_BZIP2_DECODE = 46,
+                  RCX_XCODEC_END = 47 };
 /* scratch bytes (HBM) the codec needs for nblocks blocks of <= max_block bytes.  Required for LZ4 encode, BWT and gzip
  * decode and the DEFLATE / zlib / gzip encoders; for RCX_INFLATE / RCX_ZLIB_DECODE it is what the default (wave-per-stream) decoder needs -- without it
  * rcx_launch_dev falls back to the lane-per-stream kernel (same results, slower on small batches). */

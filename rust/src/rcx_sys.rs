@@ -76,6 +76,11 @@ pub const RCX_E_GZIP_METHOD: i32 = 51;
 pub const RCX_E_GZIP_FLAGS: i32 = 52;
 pub const RCX_E_GZIP_CRC: i32 = 53;
 pub const RCX_E_GZIP_ISIZE: i32 = 54;
+pub const RCX_E_BZ2_MAGIC: i32 = 70; // rcx_bzip2_decode_batch: the first 4 bytes are not BZh1..BZh9
+pub const RCX_E_BZ2_DATA: i32 = 71;
+pub const RCX_E_BZ2_BLOCK_CRC: i32 = 72;
+pub const RCX_E_BZ2_STREAM_CRC: i32 = 73;
+pub const RCX_E_BZ2_RANDOMISED: i32 = 74;
 // enum rcx_rc
 pub const RCX_RC_OK: c_int = 0;
 pub const RCX_RC_BAD_ARG: c_int = -1;
@@ -132,7 +137,8 @@ pub const RCX_LZ4_DECODE_SHARED: c_int = 42;
 pub const RCX_INFLATE_SHARED: c_int = 43;
 pub const RCX_ZLIB_DECODE_SHARED: c_int = 44;
 pub const RCX_DICT_TRAIN: c_int = 45;
-pub const RCX_XCODEC_END: c_int = 46;
+pub const RCX_BZIP2_DECODE: c_int = 46;
+pub const RCX_XCODEC_END: c_int = 47;
 
 #[link(name = "rcx")]
 extern "C" {
@@ -190,6 +196,8 @@ extern "C" {
     // ---- dictionary training (extension): raw-content dictionaries for the calls above, one job per block
     pub fn rcx_dict_train_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, nsamples: *const u32, sample_len: *const u64, k: u32, d: u32, f: u32) -> c_int;
     pub fn rcx_dict_train_scratch_bytes(njobs: u32, max_corpus: u64, max_cap: u64, k: u32, f: u32) -> u64;
+    // ---- bzip2 (extension): block i is one whole .bz2 file, decoded to its slot
+    pub fn rcx_bzip2_decode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch) -> c_int;
     // ---- BWT / MTF / DC (src/bwt/mod.rs, mtf.rs, dc.rs)
     pub fn rcx_bwt_forward_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;
     pub fn rcx_bwt_suffixes_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;

@@ -412,6 +412,15 @@ class Context:
         """One gzip member (RFC 1952) per blob: header, DEFLATE, CRC32 + ISIZE (extension)."""
         return self._run_host("rcx_gzip_decode_batch", blobs, caps, extra_out=True)
 
+    def bzip2_decode(self, blobs, caps):
+        """One whole .bz2 file per blob (rcx_bzip2_decode_batch; extension): one or more concatenated streams, optionally followed by
+        other bytes.  status RCX_OK: outputs[i] the decoded bytes, in_used[i] the byte just after the last stream.  A cap too small
+        gives E_OUTPUT_TOO_SMALL and out_len[i] = the exact size (caps of 0: a size query); any other failure the first one in stream
+        order (E_BZ2_*, E_EOF) with out_len 0.  bzip2.decode_many does the two calls."""
+        res = self._run_host("rcx_bzip2_decode_batch", blobs, caps)
+        res.outputs = [o if st == 0 else b"" for o, st in zip(res.outputs, res.status)]     # (out_len of a slot too small is a size, not bytes)
+        return res
+
     def _deflate_encode(self, fn, blobs, caps, framing, level):
         caps = caps if caps is not None else [deflate_bound(len(b)) + framing for b in blobs]
         if level == 1:

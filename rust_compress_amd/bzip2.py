@@ -1,0 +1,104 @@
+"""bzip2 files (.bz2) as bzip2 / libbz2 write them: DECODE only, MANY FILES PER CALL.
+
+    decode_many(blobs)   every block of every file through rcx_bzip2_decode_batch: a scan for the block marks, one wave per block for the
+                         Huffman / MTF stage, the inverse BWT, the run-length undo and the CRCs, all on the device.  Two calls: the
+                         first with capacities of 0 returns the exact sizes (and every error), the second decodes into them
+    Decoder(r)           the buffered stream class in the style of compress.py: every stream up to the reader's end or up to the
+                         first bytes that are no stream header, which go back to the reader
+
+A file is one or more concatenated streams; bytes behind the last stream that do not begin with BZh1..BZh9 are left alone.  There is no
+CPU path and no encoder (writing bzip2 needs a rotation sort and a multi-table Huffman fit: not built)."""
+from . import _native as N
+from . import compress as _compress
+from .compress import CompressError
+
+
+class Bzip2Error(CompressError):
+    """A file that cannot be decoded.  index: the blob's position in the batch; what: one word for the check that failed."""
+    what = "bzip2"
+
+    def __init__(self, index, status):
+        self.index = index
+        CompressError.__init__(self, status, "bzip2 file %d: %s (%s)" % (index, self.what.replace("_", " "), N.lib().rcx_status_string(int(status)).decode()))
+
+
+class MagicError(Bzip2Error):              # the first 4 bytes are not BZh1..BZh9
+    what = "magic"
+
+
+class DataError(Bzip2Error):               # a malformed block or stream structure
+    what = "data"
+
+
+class BlockChecksumError(Bzip2Error):
+    what = "block_checksum"
+
+
+class StreamChecksumError(Bzip2Error):
+    what = "stream_checksum"
+
+
+class RandomisedError(Bzip2Error):         # the obsolete randomised bit: not supported
+    what = "randomised"
+
+
+class TruncatedError(Bzip2Error):          # the input ends inside a stream
+    what = "truncated"
+
+
+_BY_STATUS = {N.E_BZ2_MAGIC: MagicError, N.E_BZ2_DATA: DataError, N.E_BZ2_BLOCK_CRC: BlockChecksumError, N.E_BZ2_STREAM_CRC: StreamChecksumError,
+              N.E_BZ2_RANDOMISED: RandomisedError, N.E_EOF: TruncatedError}
+
+
+class FilesFailed(CompressError):
+    """decode_many without return_exceptions: results holds every file's bytes or its Bzip2Error"""
+
+    def __init__(self, results):
+        self.results = results
+        first = next(r for r in results if isinstance(r, Exception))
+        CompressError.__init__(self, first.status, str(first))
+
+
+def _error(index, status):
+    return _BY_STATUS.get(int(status), Bzip2Error)(index, int(status))
+
+
+def decode_many(blobs, ctx=None, return_exceptions=False, with_used=False):
+    """-> the decoded bytes of every file (with_used: (bytes, bytes consumed) pairs).  A file that fails raises FilesFailed, or, with
+    return_exceptions, has its typed Bzip2Error in its place."""
+    ctx = ctx or _compress.context()
+    blobs = [bytes(b) for b in blobs]
+    n = len(blobs)
+    if n == 0:
+        return []
+    sizes = ctx.bzip2_decode(blobs, [0] * n)
+    results = [None] * n
+    todo = []
+    for i in range(n):
+        st = int(sizes.status[i])
+        if st == N.E_OUTPUT_TOO_SMALL:
+            todo.append(i)
+        elif st == 0:                                       # a file that decodes to nothing
+            results[i] = (b"", int(sizes.in_used[i])) if with_used else b""
+        else:
+            results[i] = _error(i, st)
+    if todo:
+        res = ctx.bzip2_decode([blobs[i] for i in todo], [int(sizes.out_len[i]) for i in todo])
+        for k, i in enumerate(todo):
+            st = int(res.status[k])
+            results[i] = _error(i, st) if st else ((res.outputs[k], int(res.in_used[k])) if with_used else res.outputs[k])
+    if not return_exceptions and any(isinstance(r, Exception) for r in results):
+        raise FilesFailed(results)
+    return results
+
+
+class Decoder(_compress._BufferedDecoder):
+    """Reads a .bz2 file from `r`: read(n), read_to_end(), eof(), finish() as the decoders of compress.py.  Raises the Bzip2Error of
+    the first stream that fails; bytes behind the last stream go back to the reader."""
+
+    def _decode_all(self, raw):
+        res = decode_many([raw], return_exceptions=True, with_used=True)[0]
+        if isinstance(res, Exception):
+            raise res
+        self.consumed = res[1]
+        return res[0]

@@ -36,6 +36,7 @@ struct rcx_ctx {
     uint32_t param[RCX_XCODEC_END] = {0};
     DevBuf d_link;                       // rcx_lz4_decode_linked_batch: the chains' tables (order | head | dict | eff)
     DevBuf d_in, d_out, d_desc, d_scratch;
+    DevBuf d_scratch2;                   // rcx_bzip2_decode_batch: the inverse BWT's scratch, beside the stages' in d_scratch
     DevBuf d_apm;                        // apm stretch table + gate bins (filled on first use)
     uint8_t* h_desc = nullptr; size_t h_desc_cap = 0;      // page-locked: the descriptors' way in and the results' way out are small copies the call waits for
     hipStream_t copy_stream = nullptr;   // the host-memory LZ4 decode: compressed ranges on their way in under the launch that decodes them
@@ -75,7 +76,7 @@ extern "C" void rcx_ctx_destroy(rcx_ctx* c)
 {
     if (!c) return;
     (void)hipStreamSynchronize(c->stream);
-    c->d_in.release(); c->d_out.release(); c->d_desc.release(); c->d_scratch.release(); c->d_apm.release(); c->d_link.release();
+    c->d_in.release(); c->d_out.release(); c->d_desc.release(); c->d_scratch.release(); c->d_apm.release(); c->d_link.release(); c->d_scratch2.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t e : c->piece_ev) (void)hipEventDestroy(e);
@@ -143,6 +144,11 @@ extern "C" const char* rcx_status_string(int s)
     case RCX_E_GZIP_FLAGS: return "reserved gzip flags set";
     case RCX_E_GZIP_CRC: return "invalid CRC-32 on gzip member";
     case RCX_E_GZIP_ISIZE: return "invalid length on gzip member";
+    case RCX_E_BZ2_MAGIC: return "not a bzip2 file";
+    case RCX_E_BZ2_DATA: return "invalid bzip2 data";
+    case RCX_E_BZ2_BLOCK_CRC: return "invalid CRC on bzip2 block";
+    case RCX_E_BZ2_STREAM_CRC: return "invalid combined CRC on bzip2 stream";
+    case RCX_E_BZ2_RANDOMISED: return "randomised bzip2 block (not supported)";
     default: return "unknown status";
     }
 }
@@ -216,6 +222,7 @@ struct rcx_call {
     uint32_t aux_words;                  // words per block of aux_in: 1, or 2 (the zlib calls with history: lengths, then DICTIDs), or RCX_DICT_WORDS
     uint64_t dict_span;                  // shared dictionaries: one past their highest byte in the input buffer (it travels in with the blocks)
     const rcx_train_plan* train;         // dictionary training: the plan of the call (its words are aux_in), else null
+    const rcx_batch* bz2;                // bzip2 decode: the caller's batch (its host arrays steer the stages), else null
 };
 
 // ---- per-codec traits of the host path ------------------------------------------------------------------------------------------------
@@ -227,6 +234,7 @@ enum scratch_rule { SCRATCH_BY_CODEC,                                  // rcx_sc
                     SCRATCH_DEFLATE_HIST_SEGS,                         // DEFLATE levels 2..9: the real segments and the real histories
                     SCRATCH_HC_DICT_SEGS, SCRATCH_DEFLATE_DICT_SEGS,   // the real segments and the distinct dictionaries
                     SCRATCH_TRAIN,                                     // dictionary training: what the call's plan carved
+                    SCRATCH_NONE,                                      // bzip2 decode: the launch reserves d_scratch itself
                     SCRATCH_DC_OPTIONAL };                             // chunk states: none with contexts, and none when they cannot be had
 enum back_policy { BACK_USED_SPAN, BACK_INFLATE /* mirrored: the streams the first pass handed back */, BACK_CHAINS, BACK_SLOTS /* what the blocks produced, range by range */ };
 struct codec_traits {
@@ -265,6 +273,9 @@ static codec_traits traits_of(int codec, uint32_t param)
     // dictionary training writes a slot's first out_len bytes and promises the rest of the caller's buffer: nothing of the output travels
     // in, and what the jobs produced travels back slot by slot
     case RCX_DICT_TRAIN: t.back = BACK_SLOTS; t.scratch = SCRATCH_TRAIN; break;
+    // bzip2 files: a slot is written up to what the file decoded to, nothing of the output travels in; the scratch is asked for by the
+    // launch itself, which learns how many candidates there are only from its first kernel
+    case RCX_BZIP2_DECODE: t.back = BACK_SLOTS; t.scratch = SCRATCH_NONE; break;
     case RCX_DC_ENCODE: t.scratch = SCRATCH_DC_OPTIONAL; break;
     case RCX_LZ4_DECODE_LINKED: t.back = BACK_CHAINS; break;
     case RCX_ADLER32: case RCX_CRC32: case RCX_XXH32: t.needs_out = false; break;
@@ -274,7 +285,7 @@ static codec_traits traits_of(int codec, uint32_t param)
 }
 static rcx_call call_of(int codec, uint32_t param = 0, const uint32_t* aux_in = nullptr, uint32_t* aux_out = nullptr, const uint64_t* n_out = nullptr)
 {
-    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr, 0, 1, 0, nullptr};
+    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr, 0, 1, 0, nullptr, nullptr};
 }
 
 // ---- kernel arguments: built here and nowhere else ---------------------------------------------------------------------------------------
@@ -364,6 +375,16 @@ static int launch_codec(rcx_ctx* c, const rcx_call& call, rcx_kargs& k)
     case RCX_DICT_TRAIN: {                                       // k.aux: the words of rcx_plan_train; returns when the last round has run
         if (!call.train || !k.aux) { c->err = "dict train: use rcx_dict_train_batch"; return RCX_RC_BAD_ARG; }
         int rc = rcx_tu_dict_train(s, k, *call.train, c->err);
+        if (rc) return rc;
+        break; }
+    case RCX_BZIP2_DECODE: {                                     // synchronous; reserves the context's scratch itself, twice
+        if (!call.bz2) { c->err = "bzip2 decode: use rcx_bzip2_decode_batch"; return RCX_RC_BAD_ARG; }
+        const rcx_bz2_alloc alloc = {[](void* self, int which, uint64_t bytes) -> void* {
+            rcx_ctx* cc = (rcx_ctx*)self;
+            DevBuf& buf = which ? cc->d_scratch2 : cc->d_scratch;
+            if (buf.reserve(bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+            return buf.p; }, c};
+        int rc = rcx_tu_bzip2_decode(s, k, call.bz2->in_len, call.bz2->out_off, call.bz2->out_cap, alloc, c->param[RCX_BZIP2_DECODE], c->err);
         if (rc) return rc;
         break; }
     case RCX_INFLATE_HIST: case RCX_ZLIB_DECODE_DICT:            // k.aux: the history lengths (then the DICTIDs), never null
@@ -610,6 +631,7 @@ static int reserve_scratch(rcx_ctx* c, const rcx_call& call, batch_state& st)
         sb = rcx_tu_deflate_dict_scratch(n, segs, call.nhist);
         break;
     case SCRATCH_TRAIN: sb = call.train ? call.train->scratch_bytes : 0; break;
+    case SCRATCH_NONE: return RCX_RC_OK;
     case SCRATCH_DC_OPTIONAL:                                       // withctx: the wave-per-block kernel encodes, no chunk states
         sb = call.param ? 0 : rcx_scratch_bytes(call.codec, n, st.sp.max_block);
         break;
@@ -765,7 +787,13 @@ static int copy_back(rcx_ctx* c, const rcx_call& call, batch_state& st)
                 HIPCHK(c, hipMemcpyAsync(b->out_base + r.first, st.d_out + r.first, r.second - r.first, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         } else if (st.t.back == BACK_SLOTS) {
-            for (const auto& r : rcx_plan_slot_copies(st.n, b->out_off, b->out_cap, st.out_len()))
+            // (bzip2: out_len of a file that did not fit is the size it needs; its slot holds nothing to deliver)
+            std::vector<uint64_t> made;
+            if (call.codec == RCX_BZIP2_DECODE) {
+                made.assign(st.out_len(), st.out_len() + N);
+                for (size_t i = 0; i < N; i++) if (st.h_status[i] == RCX_E_OUTPUT_TOO_SMALL) made[i] = 0;
+            }
+            for (const auto& r : rcx_plan_slot_copies(st.n, b->out_off, b->out_cap, made.empty() ? st.out_len() : made.data()))
                 HIPCHK(c, hipMemcpyAsync(b->out_base + r.first, st.d_out + r.first, r.second - r.first, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         } else {
@@ -1008,6 +1036,15 @@ extern "C" int rcx_dict_train_batch(rcx_ctx* c, const rcx_batch* b, const uint32
     if (!b->nblocks) return RCX_RC_OK;
     call.aux_in = plan.aux.data(); call.aux_words = plan.aux_words; call.train = &plan;
     return run_batch(c, call, b);                                // (waits for the stream: the plan above may go)
+}
+// bzip2 files: block i is one whole file.  The stages and their read-backs are in k_bzip2.hip's launch loop; the batch goes through
+// run_batch like any other.
+extern "C" int rcx_bzip2_decode_batch(rcx_ctx* c, const rcx_batch* b)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    rcx_call call = call_of(RCX_BZIP2_DECODE);
+    call.bz2 = b;
+    return run_batch(c, call, b);
 }
 extern "C" uint64_t rcx_dict_train_scratch_bytes(uint32_t njobs, uint64_t max_corpus, uint64_t max_cap, uint32_t k, uint32_t f)
 {

@@ -6,6 +6,7 @@
 #include <string>
 #include <utility>
 #include <vector>
+#include "../../include/rcx.h"
 
 // ---- spans and limits ---------------------------------------------------------------------------------------------------------
 struct rcx_spans {
@@ -365,4 +366,75 @@ inline uint64_t rcx_plan_train_scratch(uint32_t njobs, uint64_t max_corpus, uint
 {
     if (f < 10 || f > 22 || k < 6 || k > 4096) return 0;
     return rcx_train_head_bytes(njobs) + (uint64_t)njobs * rcx_train_job_carve(max_corpus, max_cap, max_corpus, f).end + 256;
+}
+
+// ---- bzip2 (rcx_bzip2_decode_batch, k_bzip2.hip) -------------------------------------------------------------------------------------
+// The scan reports, per file and in increasing position, every place where one of the two 48-bit marks or a stream header stands; one
+// wave decodes every block mark speculatively.  The chain below strings them into streams: from bit 32 the next item must be a candidate
+// at exactly the expected bit, a block's successor is expected where its decode ended, and a mark that merely occurred inside data is
+// never reached and drops out.  Pure host code (tests/host_plan/test_plan_bz2.cpp).
+#define RCX_BZ2_BLOCK 0u                      /* the mark 0x314159265359 */
+#define RCX_BZ2_END 1u                        /* the mark 0x177245385090; extra: the 32 bits behind it, the stream's combined CRC */
+#define RCX_BZ2_HEAD 2u                       /* 'B' 'Z' 'h' '1'..'9' at a byte position; extra: the level 1..9 */
+#define RCX_BZ2_MAX_BLOCK 900000u
+#define RCX_BZ2_MAX_SELECTORS 18002u
+struct rcx_bz2_cand { uint64_t bit; uint32_t kind, extra; };                           // bit: where the mark (the 'B') starts
+struct rcx_bz2_rec { int32_t status; uint32_t nblock, orig, crc; uint64_t end_bit; };   // what the entropy stage left of a block candidate
+// the launch loop's scratch: two buffers (0: the stages', 1: the inverse BWT's) that can be asked for again, larger -- the candidates are
+// counted by the first launch, the blocks' sizes known after the entropy stage; what a buffer held is gone after the next call for it
+struct rcx_bz2_alloc { void* (*get)(void* self, int which, uint64_t bytes); void* self; };
+// somebody who watches a call (the tests' record): every candidate of the scan with its file, every block a walk accepts, every round
+struct rcx_bz2_watch {
+    void* self;
+    void (*candidate)(void* self, uint32_t file, const struct rcx_bz2_cand* c);
+    void (*live)(void* self, uint32_t file, uint64_t bit);
+    void (*round)(void* self);
+};
+struct rcx_bz2_chain {                        // one file's walk; resumable: blocks are decoded in rounds
+    uint64_t expect = 0;                      // the bit at which the next item must start
+    uint32_t level = 0, crc = 0;              // of the stream the walk is in
+    uint32_t next = 0;                        // the first candidate not passed yet
+    uint32_t streams = 0;                     // streams accepted so far
+    bool in_stream = false, done = false;
+    int32_t status = RCX_OK;                  // enum rcx_status, valid when done
+    uint64_t in_used = 0;                     // the byte just after the last accepted stream's padding
+};
+// Walks file `len` bytes long over its candidates c[0 .. n) (sorted by bit).  rec[i] is valid for the block candidates i < avail; the walk
+// stops in front of the first block candidate it needs beyond that and returns false: call again with more.  Every accepted block's
+// candidate index is appended to `live`, in stream order.  true: the walk is over, st.status and st.in_used are final.
+inline bool rcx_plan_bz2_chain(uint64_t len, const rcx_bz2_cand* c, uint32_t n, const rcx_bz2_rec* rec, uint32_t avail, rcx_bz2_chain& st,
+                               std::vector<uint32_t>& live)
+{
+    const uint64_t bits = len * 8;
+    auto fail = [&](int32_t s) { st.status = s; st.done = true; st.in_used = 0; return true; };
+    while (!st.done) {
+        if (!st.in_stream) {
+            // a stream header at byte expect / 8, or (behind an accepted stream) the end of what counts
+            while (st.next < n && (c[st.next].bit < st.expect || (c[st.next].bit == st.expect && c[st.next].kind != RCX_BZ2_HEAD))) st.next++;
+            if (st.next < n && c[st.next].bit == st.expect) {
+                st.level = c[st.next].extra; st.crc = 0; st.in_stream = true; st.expect += 32; st.next++;
+                continue;
+            }
+            if (st.streams) { st.done = true; st.status = RCX_OK; return true; }
+            return fail(len < 4 ? RCX_E_EOF : RCX_E_BZ2_MAGIC);
+        }
+        while (st.next < n && (c[st.next].bit < st.expect || (c[st.next].bit == st.expect && c[st.next].kind == RCX_BZ2_HEAD))) st.next++;
+        if (st.next >= n || c[st.next].bit != st.expect) return fail(st.expect + 48 > bits ? RCX_E_EOF : RCX_E_BZ2_DATA);
+        const rcx_bz2_cand& k = c[st.next];
+        if (k.kind == RCX_BZ2_END) {
+            if (st.expect + 80 > bits) return fail(RCX_E_EOF);
+            if (k.extra != st.crc) return fail(RCX_E_BZ2_STREAM_CRC);
+            st.in_used = (st.expect + 80 + 7) / 8; st.expect = st.in_used * 8;
+            st.in_stream = false; st.streams++; st.next++;
+            continue;
+        }
+        if (st.next >= avail) return false;
+        const rcx_bz2_rec& r = rec[st.next];
+        if (r.status) return fail(r.status);
+        if (r.nblock > 100000u * st.level || r.end_bit <= st.expect) return fail(RCX_E_BZ2_DATA);
+        live.push_back(st.next);
+        st.crc = ((st.crc << 1) | (st.crc >> 31)) ^ r.crc;
+        st.expect = r.end_bit; st.next++;
+    }
+    return true;
 }

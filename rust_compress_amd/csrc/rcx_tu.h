@@ -71,3 +71,8 @@ void rcx_tu_lz4_decode_dict(hipStream_t s, rcx_kargs& k);
 // count of finished jobs back every few rounds)
 struct rcx_train_plan;
 int rcx_tu_dict_train(hipStream_t s, rcx_kargs& k, const rcx_train_plan& plan, std::string& err);
+// tu_bzip2.hip: .bz2 files (k_bzip2.hip).  Synchronous: it reads counts back between its stages and asks `alloc` for its scratch twice
+// (the candidates are counted first).  h_*: the batch's lengths, slot offsets and capacities on the host.  Calls rcx_tu_bwt_inverse.
+struct rcx_bz2_alloc;                        // rcx_plan.h
+int rcx_tu_bzip2_decode(hipStream_t s, rcx_kargs& k, const uint64_t* h_in_len, const uint64_t* h_out_off, const uint64_t* h_out_cap,
+                        const rcx_bz2_alloc& alloc, uint32_t round, std::string& err);          // round: candidates a round, 0 = the default
