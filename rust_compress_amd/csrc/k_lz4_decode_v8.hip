@@ -134,6 +134,7 @@ struct Lz4V8 : Lz4X6<Lz4V5<1024, TC, HH, PROF8, SB, false, MIRROR>, PROF8> {
     // (3.8 of its 4.6 rounds per batch of text were the long matches').  0: off.
     static constexpr int SPLIT = SPLIT_;
     static_assert(SPLIT_ == 0 || 2 * SPLIT_ >= 64, "two entries cover the 64-byte cap");
+    static_assert(!X6 || (RCX_RUNSPLIT && SPLIT_ > 0 && SPLIT_ <= 32), "emit6 stores an entry's match as at most two frames of 16 bytes (mask table: 20 rows, a + n <= 19): no entry above 32 bytes, a run's pieces included");
     uint32_t* prog = nullptr; uint32_t wslot = 0;  // RCX_AGE_DYN: this SIMD's eight words, my wave slot
     uint32_t agerank = 0;                         // RCX_AGE_DUTY: the executor's age rank among its SIMD's four
     bool agey = true;                             // RCX_AGE_PRIO (k_lz4_decode_v5.hip): this wave is in the younger half of its SIMD's (true: the plain levels)

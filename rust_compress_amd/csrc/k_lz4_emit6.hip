@@ -25,6 +25,12 @@
 #ifndef RCX_X6_ROUNDS_ASM
 #define RCX_X6_ROUNDS_ASM 1              /* 0: emit6's copy rounds as hipcc compiles them (A/B) */
 #endif
+#ifndef RCX_X6_EARLY
+#define RCX_X6_EARLY 1                   /* emit6's HISTORY-ONLY window matches (the source ends at or below the batch's first byte once redirection is done: final since
+                                            the previous batch) are loaded before the copy rounds and go out with the gathered matches' store: 1 = all of them (a match
+                                            above 16 bytes as two frames), 2 = those of <= 16 bytes (the longer ones stay in the rounds), 0 = none (A/B: every window
+                                            match through the rounds) */
+#endif
 #ifndef RCX_V8_STAT
 #define RCX_V8_STAT(slot, v) ((void)0)                       /* the wave simulator counts batches through emit6 / emit5 here */
 #endif
@@ -281,8 +287,40 @@ struct Lz4X6 : Base {
             if (n1) store_frame<5>(fp, g0[0], g0[1], g0[2], g0[3], g1[0], a1, n1);
             if (lit2) { if (L > 16u) store_frame<5>(fp + 16, g1[0], g1[1], g1[2], g1[3], g2, a1, L - n1); }
         }
+#if RCX_X6_EARLY
+        // ---- history-only window matches: the source -- redirection is done -- ends at or below oend0, so its bytes have stood since the previous
+        // batch and nothing this batch writes can reach them (off >= M: neither a run nor a match whose second frame reads its own first).  Such a
+        // lane reads its frames here, exactly what its first (and second) copy round would read -- aligned dwords from `source - a2`, as far as 3
+        // bytes below the window's oldest byte (the 16 bytes of slack in front of the window) and, masked off in the store, past the source's end
+        // into what the literal stores are writing -- into the gathered matches' registers, goes out with their store and enters the rounds with
+        // nothing to copy: whoever waits for it alone is ready in the first round.
+        const bool early = M != 0u && !isfar && !inb && off >= M && (RCX_X6_EARLY == 1 || M <= 16u);
+        RCX_V8_STAT(15, early);
+        if (early) {
+            const int32_t sb = (int32_t)(mdst - S) - lbase - (int32_t)a2;
+#ifdef RCX_NO_MSKOR_ASM
+            const RCX_LDS_AS uint32_t* q = (const RCX_LDS_AS uint32_t*)(wb_ + (sb & ~3));
+#else
+            uint32_t qa = (uint32_t)(uintptr_t)wb_ + (uint32_t)(sb & ~3);        // (one address register, the dwords in the offset field)
+            asm volatile("" : "+v"(qa));
+            const RCX_LDS_AS uint32_t* q = (const RCX_LDS_AS uint32_t*)qa;
+#endif
+            const uint32_t sh = (uint32_t)sb & 3u;
+            const uint32_t r0 = q[0], r1 = q[1], r2 = q[2], r3 = q[3], r4 = q[4], r5 = q[5];
+            f0[0] = RCX_ALIGNBYTE(r1, r0, sh); f0[1] = RCX_ALIGNBYTE(r2, r1, sh); f0[2] = RCX_ALIGNBYTE(r3, r2, sh); f0[3] = RCX_ALIGNBYTE(r4, r3, sh);
+            f1[0] = RCX_ALIGNBYTE(r5, r4, sh);
+            if (RCX_X6_EARLY == 1 && M > 16u) {
+                const uint32_t r6 = q[6], r7 = q[7], r8 = q[8], r9 = q[9];
+                f1[1] = RCX_ALIGNBYTE(r6, r5, sh); f1[2] = RCX_ALIGNBYTE(r7, r6, sh); f1[3] = RCX_ALIGNBYTE(r8, r7, sh); f2 = RCX_ALIGNBYTE(r9, r8, sh);
+            }
+        }
+        const uint32_t mf = (isfar || early) ? M : 0u;
+        if (__ballot(mf != 0u)) {                                     // (a block's first batches: re = 0, nothing gathered, but early lanes)
+#else
+        const uint32_t mf = isfar ? M : 0u;
         if (re) {
-            const uint32_t mf = isfar ? M : 0u, n1 = mf < 16u ? mf : 16u;
+#endif
+            const uint32_t n1 = mf < 16u ? mf : 16u;
             uint8_t* fp = wb_ + (li_m - (int32_t)a2);
             if (n1) store_frame<5>(fp, f0[0], f0[1], f0[2], f0[3], f1[0], a2, n1);
             if (mf > 16u) store_frame<5>(fp + 16, f1[0], f1[1], f1[2], f1[3], f2, a2, mf - n1);
@@ -300,7 +338,7 @@ struct Lz4X6 : Base {
             const int32_t dfr = li_m - (int32_t)a2;
             const bool ovl = M != 0u && off < 16u && off < M;          // (never a gathered match: its source ends where it begins)
             const int32_t sfr = isfar ? dfr : (int32_t)(mdst - S) - lbase - (int32_t)a2;     // the source, as far back from a dword boundary as the destination (a gathered match reads itself: every lane reads)
-            const uint32_t Mc = isfar ? 0u : M;
+            const uint32_t Mc = mf ? 0u : M;                         // (gathered and early matches are stored by now: an early lane is nobody's pending producer)
             auto fill_run = [&]() __attribute__((always_inline)) {      // (called by the lanes of ready runs only: no collective inside)
                 uint32_t done = 0, back = off;                          // back: a whole number of periods, all of them standing behind the write position
                 while (done < M) {
@@ -323,7 +361,7 @@ struct Lz4X6 : Base {
             if (RCX_X6_ROUNDS_ASM) {
                 const uint32_t wa = (uint32_t)(uintptr_t)wb_;      // (low half of a generic LDS pointer = the LDS byte address)
                 const unsigned long long depx = dep | (ovl ? 1ull << lane : 0ull);
-                for (;;) {
+                while (pm) {                                       // (every window match early: no round at all)
                     pm = rcx_lz4_rounds6(wa + (uint32_t)sfr, wa + (uint32_t)dfr, Mc, (uint32_t)depx, (uint32_t)(depx >> 32), pm,
                                          (uint32_t)(uintptr_t)mtab + a2 * (4u * (uint32_t)RCX_X6_MROW), 0xffffffffu << (8u * a2));
                     if (!pm) break;
