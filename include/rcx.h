@@ -494,7 +494,7 @@ uint64_t rcx_dict_train_scratch_bytes(uint32_t njobs, uint64_t max_corpus, uint6
  *              reads, are refused (RCX_E_BZ2_RANDOMISED); and a crafted block whose L is the BWT of nothing, with a cycle through
  *              origPtr that does not divide the block's length, is RCX_E_BZ2_BLOCK_CRC here where libbz2, which walks the cycle the
  *              other way round, accepts it when the CRC is that of its own walk (no encoder writes such a block).
- *   limits     a file and a slot below 4 GiB; at most 65535 files a call (more: RCX_RC_BAD_ARG).  Decode only.
+ *   limits     a file and a slot below 4 GiB; at most 65535 files a call (more: RCX_RC_BAD_ARG).
  *   knob       rcx_ctx_set_param(ctx, RCX_BZIP2_DECODE, r): block candidates a round, 64..4096; 0 (the default) is 1536.  The one
  *              parameter of an extension id, and this call reads it.
  *   stages     a scan of every bit position for the two 48-bit marks and of every byte position for BZh1..9; one wave per block mark
@@ -506,6 +506,31 @@ uint64_t rcx_dict_train_scratch_bytes(uint32_t njobs, uint64_t max_corpus, uint6
  *              synchronous and reads counts back between the stages.  DESIGN.md 3.20 has the kernels and measurements.
  *   not here   rcx_launch_dev and rcx_multi_batch, which do not take RCX_BZIP2_DECODE. */
 int rcx_bzip2_decode_batch(rcx_ctx*, const rcx_batch*);
+/* ENCODE: block i of the batch is one whole FILE and becomes one stream in its slot -- BZh and the level digit, the blocks, the end mark,
+ * the combined CRC, padding to a byte -- that bzip2, libbz2 and rcx_bzip2_decode_batch read.  level 1..9 is the digit of the header and
+ * sets the blocks' size: a block holds C = 100000 * level - 19 bytes of run-length form, and a file is cut into chunks of as many input
+ * bytes as fill a block on the file's average, less a 64th, shorter where a chunk's own form would not fit.  One large file is many
+ * independent blocks and encodes in parallel.
+ *   bytes      those of the specification in DESIGN.md 3.21 (equal rotations by descending start, libbz2's initial partition and four
+ *              refits with Moffat-Katajainen lengths limited to 17 bits), byte for byte those of its serial reference; NOT libbz2's, whose
+ *              sorter and Huffman builder break ties their own way.  The same input, level and library give the same bytes.
+ *   results    success: RCX_OK, out_len[i] = the stream's size, in_used[i] = in_len[i].  out_cap[i] too small, 0 included:
+ *              RCX_E_OUTPUT_TOO_SMALL, out_len[i] = the exact size and NOTHING of the slot is written -- a size query, but one at the full
+ *              cost of encoding.  Nothing outside a file's own slot is ever written.  An empty file is a stream of 14 bytes.
+ *   capacity   there is no proven bound for this fit and none is exported: use in_len + in_len / 64 + 1024 as a first capacity and retry
+ *              the files that report RCX_E_OUTPUT_TOO_SMALL with the size they report (the sizes measured stay within 1 % + 8 bytes of
+ *              libbz2's; random bytes grow by about half a per cent).
+ *   limits     level outside 1..9, more than 65535 files a call: RCX_RC_BAD_ARG with rcx_last_error; a file of 4 GiB or more: the
+ *              batch path's per-block limit.  RCX_MEM_HOST and RCX_MEM_DEVICE as the decoder.
+ *   knob       rcx_ctx_set_param(ctx, RCX_BZIP2_ENCODE, r): blocks a round, 1..4096; 0 (the default) is 1024, and fewer where a round's
+ *              scratch would pass 4 GiB.  The bytes do not depend on it.
+ *   stages     the run-length step as a scan; rcx_bwt_suffixes_batch's sorter on every block doubled (T || T), of whose suffix array the
+ *              entries below n are the rotations' order; MTF chunk-parallel from last-occurrence tables; RUNA / RUNB by a scan; the
+ *              table fit, a workgroup a block; the bits MSB-first into a store; at the end every output byte gathered from the sources
+ *              that cover it.  Blocks go in rounds: the sort and the stages take some 70 bytes of scratch per input byte of a round,
+ *              the packed blocks wait for their file's end at up to 2.2 bytes per input byte of the call.  Synchronous.  DESIGN.md 3.21.
+ *   not here   randomised blocks, more than one stream a file, rcx_launch_dev and rcx_multi_batch, which do not take RCX_BZIP2_ENCODE. */
+int rcx_bzip2_encode_batch(rcx_ctx*, const rcx_batch*, int level);
 
 /* ---- device-resident descriptors (benchmark / pipeline use) ------------------ */
 /* Same kernels, but every array (offsets, lengths, status, ...) already lives
@@ -541,12 +566,13 @@ enum rcx_codec {
 };
 /* Ids of the batch entry points that rcx_launch_dev, rcx_multi_* and rcx_scratch_bytes do not take (enum rcx_codec stays as it is for
  * those): they name the entry point to rcx_ctx_set_variant / rcx_ctx_set_param, neither of which has a setting for them yet, but for
- * RCX_BZIP2_DECODE's parameter (the candidates a round, see rcx_bzip2_decode_batch). */
+ * RCX_BZIP2_DECODE's parameter (the candidates a round, see rcx_bzip2_decode_batch) and RCX_BZIP2_ENCODE's (the blocks a round, see
+ * rcx_bzip2_encode_batch). */
 enum rcx_xcodec { RCX_XXH32 = 32, RCX_LZ4_DECODE_LINKED = 33, RCX_LZ4_ENCODE_HIST = 34, RCX_DEFLATE_ENCODE_HIST = 35, RCX_ZLIB_ENCODE_DICT = 36,
                   RCX_INFLATE_HIST = 37, RCX_ZLIB_DECODE_DICT = 38, RCX_LZ4_ENCODE_SHARED = 39, RCX_DEFLATE_ENCODE_SHARED = 40,
                   RCX_ZLIB_ENCODE_SHARED = 41, RCX_LZ4_DECODE_SHARED = 42, RCX_INFLATE_SHARED = 43, RCX_ZLIB_DECODE_SHARED = 44,
-                  RCX_DICT_TRAIN = 45, RCX_BZIP2_DECODE = 46,
-                  RCX_XCODEC_END = 47 };
+                  RCX_DICT_TRAIN = 45, RCX_BZIP2_DECODE = 46, RCX_BZIP2_ENCODE = 47,
+                  RCX_XCODEC_END = 48 };
 /* scratch bytes (HBM) the codec needs for nblocks blocks of <= max_block bytes.  Required for LZ4 encode, BWT and gzip
  * decode and the DEFLATE / zlib / gzip encoders; for RCX_INFLATE / RCX_ZLIB_DECODE it is what the default (wave-per-stream) decoder needs -- without it
  * rcx_launch_dev falls back to the lane-per-stream kernel (same results, slower on small batches). */

@@ -138,7 +138,8 @@ pub const RCX_INFLATE_SHARED: c_int = 43;
 pub const RCX_ZLIB_DECODE_SHARED: c_int = 44;
 pub const RCX_DICT_TRAIN: c_int = 45;
 pub const RCX_BZIP2_DECODE: c_int = 46;
-pub const RCX_XCODEC_END: c_int = 47;
+pub const RCX_BZIP2_ENCODE: c_int = 47;
+pub const RCX_XCODEC_END: c_int = 48;
 
 #[link(name = "rcx")]
 extern "C" {
@@ -198,6 +199,7 @@ extern "C" {
     pub fn rcx_dict_train_scratch_bytes(njobs: u32, max_corpus: u64, max_cap: u64, k: u32, f: u32) -> u64;
     // ---- bzip2 (extension): block i is one whole .bz2 file, decoded to its slot
     pub fn rcx_bzip2_decode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch) -> c_int;
+    pub fn rcx_bzip2_encode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int) -> c_int;
     // ---- BWT / MTF / DC (src/bwt/mod.rs, mtf.rs, dc.rs)
     pub fn rcx_bwt_forward_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;
     pub fn rcx_bwt_suffixes_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;

@@ -2,7 +2,7 @@
 
 Only what the path needs lives here: csrc/ (HIP kernels + the C-ABI of include/rcx.h), the ctypes
 binding, the batch API, the stream-codec mirror of the reference interface (compress.py), the standard
-LZ4 frame codec (lz4frame.py), the bzip2 reader (bzip2.py) and the synthetic data generators.  There is no CPU fallback: the HIP library must be built and a GPU present.
+LZ4 frame codec (lz4frame.py), the bzip2 reader and writer (bzip2.py) and the synthetic data generators.  There is no CPU fallback: the HIP library must be built and a GPU present.
 """
 from . import _native  # noqa: F401
 from .api import BlockError, Context, DeviceBatch, RcxError, Result  # noqa: F401

@@ -54,7 +54,7 @@ EXPORTS = [
     "rcx_lz4_hc_shared_scratch_bytes", "rcx_deflate_shared_scratch_bytes",
     "rcx_lz4_decode_shared_batch", "rcx_inflate_shared_batch", "rcx_zlib_decode_shared_batch",
     "rcx_dict_train_batch", "rcx_dict_train_scratch_bytes",
-    "rcx_bzip2_decode_batch",
+    "rcx_bzip2_decode_batch", "rcx_bzip2_encode_batch",
 ]
 
 
@@ -145,6 +145,7 @@ def lib():
         L.rcx_dict_train_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
         L.rcx_dict_train_scratch_bytes.restype = C.c_uint64
         L.rcx_bzip2_decode_batch.argtypes = [C.c_void_p, C.POINTER(Batch)]
+        L.rcx_bzip2_encode_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int]
         L.rcx_deflate_level_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64]
         L.rcx_deflate_level_scratch_bytes.restype = C.c_uint64
         for name in ("rcx_inflate_batch", "rcx_zlib_decode_batch", "rcx_adler32_batch", "rcx_crc32_batch",

@@ -421,6 +421,14 @@ class Context:
         res.outputs = [o if st == 0 else b"" for o, st in zip(res.outputs, res.status)]     # (out_len of a slot too small is a size, not bytes)
         return res
 
+    def bzip2_encode(self, blobs, caps, level=9):
+        """One whole .bz2 file per blob (rcx_bzip2_encode_batch; extension): one stream at level 1..9.  status RCX_OK: outputs[i] the
+        stream.  A cap too small gives E_OUTPUT_TOO_SMALL and out_len[i] = the exact size, at the full cost of encoding; there is no
+        bound to ask for: bzip2.encode_many starts at n + n / 64 + 1024 and retries."""
+        res = self._run_host("rcx_bzip2_encode_batch", blobs, caps, scalar=int(level))
+        res.outputs = [o if st == 0 else b"" for o, st in zip(res.outputs, res.status)]
+        return res
+
     def _deflate_encode(self, fn, blobs, caps, framing, level):
         caps = caps if caps is not None else [deflate_bound(len(b)) + framing for b in blobs]
         if level == 1:

@@ -1,4 +1,4 @@
-"""bzip2 files (.bz2) as bzip2 / libbz2 write them: DECODE only, MANY FILES PER CALL.
+"""bzip2 files (.bz2) as bzip2 / libbz2 write and read them, MANY FILES PER CALL.
 
     decode_many(blobs)   every block of every file through rcx_bzip2_decode_batch: a scan for the block marks, one wave per block for the
                          Huffman / MTF stage, the inverse BWT, the run-length undo and the CRCs, all on the device.  Two calls: the
@@ -6,8 +6,14 @@
     Decoder(r)           the buffered stream class in the style of compress.py: every stream up to the reader's end or up to the
                          first bytes that are no stream header, which go back to the reader
 
-A file is one or more concatenated streams; bytes behind the last stream that do not begin with BZh1..BZh9 are left alone.  There is no
-CPU path and no encoder (writing bzip2 needs a rotation sort and a multi-table Huffman fit: not built)."""
+    encode_many(datas)   every file as one stream through rcx_bzip2_encode_batch: the run-length step, a suffix sort of every block
+                         doubled, MTF, the table fit and the bit packing, all on the device.  One call with capacities of
+                         n + n / 64 + 1024, one retry for the files that report a larger size
+    Encoder(w)           the buffering stream class in the style of compress.py's DEFLATE encoders: one stream at finish()
+
+A file that is read is one or more concatenated streams; bytes behind the last stream that do not begin with BZh1..BZh9 are left alone.
+A file that is written is one stream whose bytes are those of the specification in DESIGN.md 3.21, not libbz2's (every bzip2 reader
+reads them).  There is no CPU path."""
 from . import _native as N
 from . import compress as _compress
 from .compress import CompressError
@@ -102,3 +108,57 @@ class Decoder(_compress._BufferedDecoder):
             raise res
         self.consumed = res[1]
         return res[0]
+
+
+def _level(level):
+    if not 1 <= int(level) <= 9:
+        raise ValueError("bzip2 level must be 1..9")
+    return int(level)
+
+
+def encode_many(datas, level=9, ctx=None):
+    """-> one .bz2 stream per input, at level 1..9 (blocks of 100 000 x level bytes).  There is no bound to size the slots with: the first
+    call offers n + n / 64 + 1024 bytes each, and a file that needs more says how much and is encoded again."""
+    level = _level(level)
+    ctx = ctx or _compress.context()
+    datas = [bytes(d) for d in datas]
+    if not datas:
+        return []
+    res = ctx.bzip2_encode(datas, [len(d) + len(d) // 64 + 1024 for d in datas], level)
+    out = list(res.outputs)
+    todo = []
+    for i, st in enumerate(res.status[:len(datas)]):
+        if int(st) == N.E_OUTPUT_TOO_SMALL:
+            todo.append(i)
+        elif int(st):
+            raise CompressError(int(st), "bzip2 file %d: %s" % (i, N.lib().rcx_status_string(int(st)).decode()))
+    if todo:
+        again = ctx.bzip2_encode([datas[i] for i in todo], [int(res.out_len[i]) for i in todo], level)
+        for k, i in enumerate(todo):
+            if int(again.status[k]):
+                raise CompressError(int(again.status[k]), "bzip2 file %d: %s" % (i, N.lib().rcx_status_string(int(again.status[k])).decode()))
+            out[i] = again.outputs[k]
+    return out
+
+
+class Encoder:
+    """Writes a .bz2 file to `w`.  Shaped like compress.py's DEFLATE encoders: write() only buffers, and finish() encodes everything as
+    ONE stream in one batch call, writes it to the writer and returns the writer.  level: 1..9; anything else raises ValueError."""
+
+    def __init__(self, w, level=9):
+        self.w = w
+        self.buf = bytearray()
+        self.level = _level(level)
+
+    def write(self, buf):
+        self.buf += bytes(buf)
+        return len(buf)
+
+    def flush(self):
+        pass
+
+    def finish(self):
+        out = encode_many([bytes(self.buf)], self.level)[0]
+        self.buf = bytearray()
+        self.w.write(out)
+        return self.w

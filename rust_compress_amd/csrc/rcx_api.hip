@@ -36,7 +36,8 @@ struct rcx_ctx {
     uint32_t param[RCX_XCODEC_END] = {0};
     DevBuf d_link;                       // rcx_lz4_decode_linked_batch: the chains' tables (order | head | dict | eff)
     DevBuf d_in, d_out, d_desc, d_scratch;
-    DevBuf d_scratch2;                   // rcx_bzip2_decode_batch: the inverse BWT's scratch, beside the stages' in d_scratch
+    DevBuf d_scratch2;                   // rcx_bzip2_decode_batch: the inverse BWT's scratch, beside the stages' in d_scratch (rcx_bzip2_encode_batch: the sort's)
+    DevBuf d_scratch3;                   // rcx_bzip2_encode_batch: what lasts for the call, the blocks' records and their packed bits
     DevBuf d_apm;                        // apm stretch table + gate bins (filled on first use)
     uint8_t* h_desc = nullptr; size_t h_desc_cap = 0;      // page-locked: the descriptors' way in and the results' way out are small copies the call waits for
     hipStream_t copy_stream = nullptr;   // the host-memory LZ4 decode: compressed ranges on their way in under the launch that decodes them
@@ -76,7 +77,7 @@ extern "C" void rcx_ctx_destroy(rcx_ctx* c)
 {
     if (!c) return;
     (void)hipStreamSynchronize(c->stream);
-    c->d_in.release(); c->d_out.release(); c->d_desc.release(); c->d_scratch.release(); c->d_apm.release(); c->d_link.release(); c->d_scratch2.release();
+    c->d_in.release(); c->d_out.release(); c->d_desc.release(); c->d_scratch.release(); c->d_apm.release(); c->d_link.release(); c->d_scratch2.release(); c->d_scratch3.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t e : c->piece_ev) (void)hipEventDestroy(e);
@@ -222,7 +223,7 @@ struct rcx_call {
     uint32_t aux_words;                  // words per block of aux_in: 1, or 2 (the zlib calls with history: lengths, then DICTIDs), or RCX_DICT_WORDS
     uint64_t dict_span;                  // shared dictionaries: one past their highest byte in the input buffer (it travels in with the blocks)
     const rcx_train_plan* train;         // dictionary training: the plan of the call (its words are aux_in), else null
-    const rcx_batch* bz2;                // bzip2 decode: the caller's batch (its host arrays steer the stages), else null
+    const rcx_batch* bz2;                // bzip2 decode and encode: the caller's batch (its host arrays steer the stages), else null
 };
 
 // ---- per-codec traits of the host path ------------------------------------------------------------------------------------------------
@@ -276,6 +277,8 @@ static codec_traits traits_of(int codec, uint32_t param)
     // bzip2 files: a slot is written up to what the file decoded to, nothing of the output travels in; the scratch is asked for by the
     // launch itself, which learns how many candidates there are only from its first kernel
     case RCX_BZIP2_DECODE: t.back = BACK_SLOTS; t.scratch = SCRATCH_NONE; break;
+    // ... and written: a slot holds its stream or, too small, nothing; the launch reserves its three buffers itself
+    case RCX_BZIP2_ENCODE: t.back = BACK_SLOTS; t.scratch = SCRATCH_NONE; break;
     case RCX_DC_ENCODE: t.scratch = SCRATCH_DC_OPTIONAL; break;
     case RCX_LZ4_DECODE_LINKED: t.back = BACK_CHAINS; break;
     case RCX_ADLER32: case RCX_CRC32: case RCX_XXH32: t.needs_out = false; break;
@@ -385,6 +388,17 @@ static int launch_codec(rcx_ctx* c, const rcx_call& call, rcx_kargs& k)
             if (buf.reserve(bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
             return buf.p; }, c};
         int rc = rcx_tu_bzip2_decode(s, k, call.bz2->in_len, call.bz2->out_off, call.bz2->out_cap, alloc, c->param[RCX_BZIP2_DECODE], c->err);
+        if (rc) return rc;
+        break; }
+    case RCX_BZIP2_ENCODE: {                                     // synchronous; the codec parameter: the level; reserves the context's scratch itself
+        if (!call.bz2) { c->err = "bzip2 encode: use rcx_bzip2_encode_batch"; return RCX_RC_BAD_ARG; }
+        const rcx_bz2_alloc alloc = {[](void* self, int which, uint64_t bytes) -> void* {
+            rcx_ctx* cc = (rcx_ctx*)self;
+            DevBuf& buf = which == 2 ? cc->d_scratch3 : which ? cc->d_scratch2 : cc->d_scratch;
+            if (buf.reserve(bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+            return buf.p; }, c};
+        int rc = rcx_tu_bzip2_encode(s, k, call.bz2->in_off, call.bz2->in_len, call.bz2->out_off, call.bz2->out_cap, alloc, (int)call.param,
+                                     c->param[RCX_BZIP2_ENCODE], c->err);
         if (rc) return rc;
         break; }
     case RCX_INFLATE_HIST: case RCX_ZLIB_DECODE_DICT:            // k.aux: the history lengths (then the DICTIDs), never null
@@ -789,7 +803,7 @@ static int copy_back(rcx_ctx* c, const rcx_call& call, batch_state& st)
         } else if (st.t.back == BACK_SLOTS) {
             // (bzip2: out_len of a file that did not fit is the size it needs; its slot holds nothing to deliver)
             std::vector<uint64_t> made;
-            if (call.codec == RCX_BZIP2_DECODE) {
+            if (call.codec == RCX_BZIP2_DECODE || call.codec == RCX_BZIP2_ENCODE) {
                 made.assign(st.out_len(), st.out_len() + N);
                 for (size_t i = 0; i < N; i++) if (st.h_status[i] == RCX_E_OUTPUT_TOO_SMALL) made[i] = 0;
             }
@@ -1043,6 +1057,17 @@ extern "C" int rcx_bzip2_decode_batch(rcx_ctx* c, const rcx_batch* b)
 {
     if (!c) return RCX_RC_BAD_ARG;
     rcx_call call = call_of(RCX_BZIP2_DECODE);
+    call.bz2 = b;
+    return run_batch(c, call, b);
+}
+// ... and written: block i is one whole file and becomes one stream.  The launch loop in k_bzip2_enc.hip plans the blocks from the host
+// arrays of the caller's batch, whose offsets are the same in the staged copy.
+extern "C" int rcx_bzip2_encode_batch(rcx_ctx* c, const rcx_batch* b, int level)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    if (level < 1 || level > 9) { c->err = "bzip2 encode: level must be 1..9"; return RCX_RC_BAD_ARG; }
+    if (b && b->nblocks > 65535u) { c->err = "bzip2 encode: at most 65535 files a call"; return RCX_RC_BAD_ARG; }
+    rcx_call call = call_of(RCX_BZIP2_ENCODE, (uint32_t)level);
     call.bz2 = b;
     return run_batch(c, call, b);
 }

@@ -438,3 +438,117 @@ inline bool rcx_plan_bz2_chain(uint64_t len, const rcx_bz2_cand* c, uint32_t n, 
     }
     return true;
 }
+
+// ---- bzip2 encode (rcx_bzip2_encode_batch, k_bzip2_enc.hip) ----------------------------------------------------------
+// One file is one stream.  A block holds C bytes of run-length form (C = 100000 * level - 19; the tests pass smaller ones).  A file of L
+// bytes is cut into chunks of s input bytes, the last one shorter, and every chunk is one block.  s is what fills a block on the file's
+// average, less a 64th: q = floor(C L / R), R the sum of the run-length forms of the file's pieces of C input bytes, each measured on its
+// own, and s = q - q / 64 -- about 0.98 C for text, 0.82 C where five bytes become six, many times C for long runs, as libbz2's
+// greedy cut takes them.  While the longest form of a chunk is over C, s becomes min(s - 1, q' - q' / 64) with q' = floor(s C / longest),
+// and from the fifth such turn on at most s / 2 as well: s starts at 2^30 or less, so 4 + 30 shortenings reach one byte, which always
+// fits, and a file is measured 1 + 35 times at the very most (a file whose stretches differ wildly; two times is the rule).  The cut
+// is not greedy: every block is known before any is encoded.
+// Pure host code (tests/host_plan/test_plan_bz2_enc.cpp).
+#define RCX_BZ2E_ROUND 1024u                  /* blocks a round unless the caller says otherwise */
+#define RCX_BZ2E_ROUND_MAX 4096u
+#define RCX_BZ2E_HEAD_BITS 32u                /* 'B' 'Z' 'h' level */
+#define RCX_BZ2E_TAIL_BITS 80u                /* the end mark and the combined CRC */
+struct rcx_bz2e_block {
+    uint32_t file;
+    uint32_t len;                             // input bytes
+    uint64_t off;                             // where they start in the file
+    uint32_t n;                               // the length of the run-length form (0: not measured yet)
+    uint32_t pad;
+};
+// what the stages leave of a block: the CRC over its input bytes, origPtr, the symbols with the end symbol, the tables and selectors, the
+// bits in front of the symbols and the block's bits in all, the used-byte map (bit b of word b / 32)
+struct rcx_bz2e_hdr { uint32_t crc, orig, nmtf, ngroups, nsel, alpha, head_bits, bits; uint32_t used[8]; };
+// somebody who watches a call (the tests' record): every block behind its round with the stage arrays -- T, L, the symbols, the lengths
+// (6 x 258) and the selectors AS THE DEVICE HOLDS THEM, so only a harness whose device memory is the host's can read them -- and every round
+struct rcx_bz2e_watch {
+    void* self;
+    void (*block)(void* self, uint32_t index, const struct rcx_bz2e_block* b, const uint8_t* T, const uint8_t* L, const struct rcx_bz2e_hdr* h,
+                  const uint16_t* syms, const uint8_t* lens, const uint8_t* sel);
+    void (*round)(void* self);
+};
+// the measuring pieces (C input bytes each, the last one shorter) of every file, in file order; an empty file has none.  false: a file
+// of 4 GiB or more
+inline bool rcx_plan_bz2e_chunks(uint32_t nfiles, const uint64_t* in_len, uint32_t C, std::vector<rcx_bz2e_block>& out, std::string& err)
+{
+    out.clear();
+    for (uint32_t f = 0; f < nfiles; f++) {
+        if (in_len[f] >> 32) { err = "block " + std::to_string(f) + ": lengths of 4 GiB or more are not supported (per-block limit 2^32 - 1 bytes)"; return false; }
+        for (uint64_t o = 0; o < in_len[f]; o += C)
+            out.push_back(rcx_bz2e_block{f, (uint32_t)std::min<uint64_t>(C, in_len[f] - o), o, 0u, 0u});
+    }
+    return true;
+}
+// input bytes a chunk of a file of len > 0 bytes starts with, from the sum of its pieces' run-length forms (rle_sum > 0): 2^30 at the
+// most, whatever the runs (the kernels index a chunk with 32 bits, with room to step past its end)
+#define RCX_BZ2E_MAX_CHUNK (1ull << 30)
+inline uint64_t rcx_plan_bz2e_step(uint64_t len, uint64_t rle_sum, uint32_t C)
+{
+    const uint64_t q = (uint64_t)C * len / rle_sum, s = q - q / 64;
+    return std::min<uint64_t>(std::min<uint64_t>(std::max<uint64_t>(s, 1), len), RCX_BZ2E_MAX_CHUNK);
+}
+// ... and the next, smaller one when the longest form of a chunk did not fit; turn: how often s has been shortened already
+#define RCX_BZ2E_TURNS 36u                    /* probes of the chunk length at the most: the first, 4 in proportion, 30 halvings, one to spare */
+inline uint64_t rcx_plan_bz2e_less(uint64_t s, uint32_t longest, uint32_t C, uint32_t turn)
+{
+    const uint64_t q = s * C / longest;
+    uint64_t t = std::min<uint64_t>(s - 1, q - q / 64);
+    if (turn >= 4) t = std::min<uint64_t>(t, s / 2);
+    return std::max<uint64_t>(t, 1);
+}
+// appends the chunks of file f, len bytes long, at s input bytes a chunk, n = 0: to be measured
+inline void rcx_plan_bz2e_cut(uint32_t f, uint64_t len, uint64_t s, std::vector<rcx_bz2e_block>& out)
+{
+    for (uint64_t o = 0; o < len; o += s) out.push_back(rcx_bz2e_block{f, (uint32_t)std::min<uint64_t>(s, len - o), o, 0u, 0u});
+}
+// rounds: cuts[r] .. cuts[r + 1] are the blocks of round r, `per_round` at the most
+inline void rcx_plan_bz2e_rounds(uint32_t nblocks, uint32_t per_round, std::vector<uint32_t>& cuts)
+{
+    cuts.assign(1, 0u);
+    if (!per_round) per_round = 1;
+    for (uint32_t b = 0; b < nblocks;) { b = (uint32_t)std::min<uint64_t>((uint64_t)b + per_round, nblocks); cuts.push_back(b); }
+}
+struct rcx_bz2e_file {
+    uint32_t first, count;                    // its blocks
+    uint32_t crc;                             // the combined CRC: c = rotl(c, 1) ^ crc of every block in order
+    int32_t status;                           // RCX_OK, or RCX_E_OUTPUT_TOO_SMALL: nothing of it is written
+    uint64_t bits;                            // header, blocks and trailer, without the padding
+    uint64_t out_len;                         // the stream's size in bytes
+};
+// Where every block's bits start in its file's stream (bit_off, behind the 32 header bits), and every file's size, combined CRC and
+// status against its capacity.  bits / crc: per block, what the fit and the run-length stage left.
+inline void rcx_plan_bz2e_layout(uint32_t nfiles, const std::vector<rcx_bz2e_block>& blocks, const uint64_t* bits, const uint32_t* crc,
+                                 const uint64_t* out_cap, std::vector<uint64_t>& bit_off, std::vector<rcx_bz2e_file>& files)
+{
+    bit_off.assign(blocks.size(), 0);
+    files.assign(nfiles, rcx_bz2e_file{0u, 0u, 0u, RCX_OK, 0ull, 0ull});
+    size_t b = 0;
+    for (uint32_t f = 0; f < nfiles; f++) {
+        rcx_bz2e_file& F = files[f];
+        F.first = (uint32_t)b;
+        uint64_t at = RCX_BZ2E_HEAD_BITS;
+        uint32_t c = 0;
+        for (; b < blocks.size() && blocks[b].file == f; b++) {
+            bit_off[b] = at;
+            at += bits[b];
+            c = ((c << 1) | (c >> 31)) ^ crc[b];
+        }
+        F.count = (uint32_t)b - F.first;
+        F.crc = c;
+        F.bits = at + RCX_BZ2E_TAIL_BITS;
+        F.out_len = (F.bits + 7) / 8;
+        F.status = F.out_len <= out_cap[f] ? RCX_OK : RCX_E_OUTPUT_TOO_SMALL;
+    }
+}
+// what a block's bits take at the most, in bytes with the slack the packer's and the joiner's word accesses need: 17 bits a symbol (the
+// block's bytes and the end symbol), a selector of 6 bits per 50 symbols, six tables of 258 delta-coded lengths, the fixed fields
+inline uint64_t rcx_plan_bz2e_block_bound(uint32_t n)
+{
+    const uint64_t nsym = (uint64_t)n + 1, nsel = (nsym + 49) / 50;
+    const uint64_t bits = 17 * nsym + 6 * nsel + 6ull * (5 + 258 * 33) + 48 + 32 + 1 + 24 + 16 + 256 + 3 + 15;
+    return ((bits + 31) / 32) * 4 + 16;
+}

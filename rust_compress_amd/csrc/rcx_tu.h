@@ -76,3 +76,7 @@ int rcx_tu_dict_train(hipStream_t s, rcx_kargs& k, const rcx_train_plan& plan, s
 struct rcx_bz2_alloc;                        // rcx_plan.h
 int rcx_tu_bzip2_decode(hipStream_t s, rcx_kargs& k, const uint64_t* h_in_len, const uint64_t* h_out_off, const uint64_t* h_out_cap,
                         const rcx_bz2_alloc& alloc, uint32_t round, std::string& err);          // round: candidates a round, 0 = the default
+// tu_bzip2_enc.hip: whole files to .bz2 streams (k_bzip2_enc.hip).  Synchronous: it reads the chunks' lengths and the blocks' records
+// back and asks `alloc` for three buffers (0: the stages', 1: the sort's, 2: what lasts for the call).  Calls rcx_tu_bwt_forward.
+int rcx_tu_bzip2_encode(hipStream_t s, rcx_kargs& k, const uint64_t* h_in_off, const uint64_t* h_in_len, const uint64_t* h_out_off,
+                        const uint64_t* h_out_cap, const rcx_bz2_alloc& alloc, int level, uint32_t round, std::string& err);   // round: blocks a round, 0 = the default
