@@ -14,7 +14,10 @@
  *   - struct-of-arrays batch descriptors: block i reads
  *     in_base[in_off[i] .. in_off[i]+in_len[i]) and writes at most out_cap[i]
  *     bytes at out_base[out_off[i]..]; the callee allocates nothing the caller
- *     keeps, and retains no pointer after return.
+ *     keeps, and retains no pointer after return.  No byte of `out_base`
+ *     outside the slots is written, from either memory kind; inside a slot,
+ *     bytes beyond `out_len[i]` are unspecified unless an entry point says
+ *     otherwise.
  *   - `mem` says where the DATA buffers (in_base/out_base) live:
  *       RCX_MEM_DEVICE: HBM pointers (hipMalloc / torch.cuda tensors);
  *       RCX_MEM_HOST:   host pointers; the library stages them through HBM.
@@ -403,14 +406,20 @@ int rcx_bwt_inverse_minimal_batch(rcx_ctx*, const rcx_batch*, const uint32_t* or
 int rcx_mtf_encode_batch(rcx_ctx*, const rcx_batch*);
 int rcx_mtf_decode_batch(rcx_ctx*, const rcx_batch*);
 /* reference: src/bwt/dc.rs:110-159 encode_simple::<u32> order: out block i =
- * little-endian u32 words: 256 x init, then k distances (out_len = 4*(256+k)) */
+ * little-endian u32 words: 256 x init, then k distances (out_len = 4*(256+k)).
+ * The slot is the encoder's work array: it must hold 4*(256+n) bytes (n = in_len[i]; less: RCX_E_OUTPUT_TOO_SMALL) and be
+ * 4-BYTE ALIGNED -- the kernels address the words as uint32_t.  With RCX_MEM_DEVICE that is the address out_base + out_off[i],
+ * with RCX_MEM_HOST the offset out_off[i] (the bytes are staged at an aligned address).  The batch calls refuse a word buffer
+ * anywhere else with RCX_RC_BAD_ARG and rcx_last_error names the block; through rcx_launch_dev such a block gets
+ * RCX_E_OUTPUT_TOO_SMALL (encode) or RCX_E_MALFORMED (decode) and the rest of the batch is coded. */
 int rcx_dc_encode_batch(rcx_ctx*, const rcx_batch*);
-/* reference: src/bwt/dc.rs:162-252 decode_simple; in = the words above,
- * n_out[i] = decoded length n (dc carries no length itself) */
+/* reference: src/bwt/dc.rs:162-252 decode_simple; in = the words above (4-byte aligned in the same sense: in_base + in_off[i],
+ * or in_off[i] from host memory), n_out[i] = decoded length n (dc carries no length itself) */
 int rcx_dc_decode_batch(rcx_ctx*, const rcx_batch*, const uint64_t* n_out);
 /* The same two with the coding CONTEXT of every distance (reference: src/bwt/dc.rs:40-58 `Context`; yielded next to each
  * distance by EncodeIterator :88-103, handed to decode's distance callback :199-229; the reference's test :268-289 checks
  * that the two sides see the same contexts).  A context is 8 bytes: u32 LE symbol | last_rank << 8, u32 LE distance_limit.
+ * The word buffers (the encoder's slot, the decoder's input) are 4-byte aligned as above, and a misaligned one is refused the same way.
  *   encode: block i's slot must hold 4*(256+n) + 8*n bytes (n = in_len[i]); words as above in its first 4*(256+k) bytes,
  *           the k contexts from byte 4*(256+n) on; out_len[i] = 4*(256+n) + 8*k.
  *   decode: the slot must be 8-byte aligned and hold ((n+7)&~7) + 8*(in_len[i]/4 - 256) bytes; the n decoded bytes first,

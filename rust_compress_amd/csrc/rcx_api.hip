@@ -497,9 +497,31 @@ struct batch_state {
     void* scratch = nullptr; uint64_t scratch_bytes = 0;
     rcx_kargs k = {};
     bool gated = false;
+    bool out_gaps = false;                                           // bytes of [0, out_span) lie outside every slot: they are the caller's
+    bool out_staged = false;                                         // ... and were staged in, so that the span copy takes them back
     const uint64_t* out_len() const { return h64 + 5 * (size_t)n; }
 };
 #define STAGE(x) do { const int rc_ = (x); if (rc_ != RCX_RC_OK) return rc_; } while (0)
+
+// The DC kernels address their words through uint32_t pointers (k_serial.hip; include/rcx.h asks for the alignment): a word buffer at
+// another address is the caller's error and is refused by the block's number (the kernels themselves, reached through rcx_launch_dev,
+// give such a block RCX_E_OUTPUT_TOO_SMALL / RCX_E_MALFORMED).  A host-memory batch is staged at an aligned address: there the
+// offset alone decides.  rcx_multi_batch asks before it rebases its ranges' offsets, so that it refuses what one context refuses.
+static bool dc_words_aligned(int codec, const rcx_batch* b, std::string& err)
+{
+    if (codec != RCX_DC_ENCODE && codec != RCX_DC_DECODE) return true;
+    const bool enc = codec == RCX_DC_ENCODE;
+    const uint64_t* off = enc ? b->out_off : b->in_off;
+    if (!off) return true;
+    const uintptr_t base = b->mem == RCX_MEM_HOST ? 0 : (uintptr_t)(enc ? (const uint8_t*)b->out_base : b->in_base);
+    for (uint32_t i = 0; i < b->nblocks; i++)
+        if ((base + off[i]) & 3u) {
+            err = std::string(enc ? "dc encode" : "dc decode") + ": block " + std::to_string(i) + ": the word buffer is not 4-byte aligned ("
+                + (enc ? "out_off" : "in_off") + (b->mem == RCX_MEM_HOST ? " must be a multiple of 4)" : ", added to the base address, must be a multiple of 4)");
+            return false;
+        }
+    return true;
+}
 
 // stage 1: the arguments, the spans and the per-block limits
 static int check_batch(rcx_ctx* c, const rcx_call& call, const rcx_batch* b, batch_state& st)
@@ -514,6 +536,12 @@ static int check_batch(rcx_ctx* c, const rcx_call& call, const rcx_batch* b, bat
     if (call.dict_span > st.sp.in_span) st.sp.in_span = call.dict_span;      // (the dictionaries' ranges travel in with the blocks')
     if ((st.sp.in_span && !b->in_base) || (st.sp.out_span && !b->out_base)) { c->err = "null data pointer"; return RCX_RC_BAD_ARG; }
     if (b->mem != RCX_MEM_HOST && b->mem != RCX_MEM_DEVICE) { c->err = "bad mem kind"; return RCX_RC_BAD_ARG; }
+    if (!dc_words_aligned(call.codec, b, c->err)) return RCX_RC_BAD_ARG;
+    // no byte of the caller's output buffer outside the slots is written (include/rcx.h).  The span that travels back from the staging
+    // buffer covers slots alone when the layout is dense (rcx_plan_out_dense: bench.py's and every fixed-slot layout), and the call is
+    // what it always was; any other layout is marked here, and stage_in_out / copy_back keep the caller's bytes
+    st.out_gaps = b->mem == RCX_MEM_HOST && call.needs_out && !st.t.preload_out && (st.t.back == BACK_USED_SPAN || st.t.back == BACK_INFLATE) &&
+                  !rcx_plan_out_dense(st.n, b->out_off, b->out_cap, st.sp.out_span);
     return RCX_RC_OK;
 }
 
@@ -565,7 +593,11 @@ static int stage_in_out(rcx_ctx* c, const rcx_call& call, batch_state& st)
     if (st.sp.in_span && st.pieces <= 1) HIPCHK(c, hipMemcpyAsync(c->d_in.p, b->in_base, st.sp.in_span, hipMemcpyHostToDevice, s));
     st.d_in = (const uint8_t*)c->d_in.p;
     st.d_out = (uint8_t*)c->d_out.p + out_shift;
-    if (st.t.preload_out && st.sp.out_span) HIPCHK(c, hipMemcpyAsync(st.d_out, b->out_base, st.sp.out_span, hipMemcpyHostToDevice, s));
+    // a layout with gaps: the span copy back must return the caller's own bytes, so the span travels in first -- unless the launch
+    // stores into the caller's page-locked buffer itself and no span travels back (copy_back takes the slots alone should the launch
+    // decline the mirror after all)
+    st.out_staged = st.out_gaps && !st.mirror;
+    if ((st.t.preload_out || st.out_staged) && st.sp.out_span) HIPCHK(c, hipMemcpyAsync(st.d_out, b->out_base, st.sp.out_span, hipMemcpyHostToDevice, s));
     // the linked LZ4 decoder reads the dictionaries the caller put in front of the chain heads' slots: those ranges alone travel in
     // (and only what the chains wrote travels back, copy_back)
     if (call.link) {
@@ -773,7 +805,7 @@ static int copy_back_handed_back(rcx_ctx* c, const rcx_call& call, batch_state& 
     HIPCHK(c, hipMemcpy(&nfb, marks, 4, hipMemcpyDeviceToHost));
     if (!nfb) return RCX_RC_OK;
     const uint64_t* ol = st.out_len();
-    if (nfb > n / 8u + 16u) {
+    if (nfb > n / 8u + 16u && !st.out_gaps) {                         // (the span only where it covers slots alone: rcx_plan_out_dense)
         const uint64_t used_span = rcx_plan_used_span(n, b->out_off, b->out_cap, ol);
         if (used_span) HIPCHK(c, hipMemcpy(b->out_base, st.d_out, used_span, hipMemcpyDeviceToHost));
         return RCX_RC_OK;
@@ -808,6 +840,11 @@ static int copy_back(rcx_ctx* c, const rcx_call& call, batch_state& st)
                 for (size_t i = 0; i < N; i++) if (st.h_status[i] == RCX_E_OUTPUT_TOO_SMALL) made[i] = 0;
             }
             for (const auto& r : rcx_plan_slot_copies(st.n, b->out_off, b->out_cap, made.empty() ? st.out_len() : made.data()))
+                HIPCHK(c, hipMemcpyAsync(b->out_base + r.first, st.d_out + r.first, r.second - r.first, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        } else if (st.out_gaps && !st.out_staged) {
+            // (a launch that declined the mirror on a layout with gaps: nothing of the caller's buffer was staged, so what the blocks produced)
+            for (const auto& r : rcx_plan_slot_copies(st.n, b->out_off, b->out_cap, st.out_len()))
                 HIPCHK(c, hipMemcpyAsync(b->out_base + r.first, st.d_out + r.first, r.second - r.first, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         } else {
@@ -1310,6 +1347,7 @@ extern "C" int rcx_multi_batch(rcx_multi* m, int codec, const rcx_batch* b, cons
     if (!m || m->ctx.empty()) return RCX_RC_BAD_ARG;
     if (!b || (b->nblocks && (!b->in_off || !b->in_len || !b->status))) { m->err = "null descriptor array"; return RCX_RC_BAD_ARG; }
     if (b->mem != RCX_MEM_HOST) { m->err = "rcx_multi_batch takes host-memory batches (device-resident ranges: rcx_multi_launch_dev)"; return RCX_RC_BAD_ARG; }
+    if (!dc_words_aligned(codec, b, m->err)) return RCX_RC_BAD_ARG;      // (before the ranges' offsets are rebased: what one context refuses)
     const uint32_t n = b->nblocks, G = (uint32_t)m->ctx.size();
     if (n == 0) return RCX_RC_OK;
     const bool has_out = b->out_off && b->out_cap;

@@ -212,6 +212,32 @@ inline uint64_t rcx_plan_used_span(uint32_t n, const uint64_t* out_off, const ui
     }
     return used;
 }
+// Is every byte of [0, out_span) inside some block's slot [out_off[i], out_off[i] + out_cap[i])?  (out_span: rcx_plan_spans', one past
+// the highest slot byte.)  Then one copy of the used span from a staging buffer touches nothing but slots, whose bytes beyond out_len
+// are unspecified; otherwise it would replace the caller's bytes in front of, between and behind the slots (run_batch stages the output
+// span in first for such a layout).  A dense layout in address order, which is how every packer lays its slots out, is recognised in
+// one pass without an allocation; anything else by a sort of the slots.  Slots of capacity 0 cover nothing; overlapping slots cover
+// their union.
+inline bool rcx_plan_out_dense(uint32_t n, const uint64_t* out_off, const uint64_t* out_cap, uint64_t out_span)
+{
+    uint64_t at = 0;
+    uint32_t i = 0;
+    for (; i < n; i++) {
+        if (!out_cap[i]) continue;
+        if (out_off[i] > at) break;                            // a gap, unless a later slot fills it: the sort below decides
+        if (out_off[i] + out_cap[i] > at) at = out_off[i] + out_cap[i];
+    }
+    if (i == n) return at == out_span;
+    std::vector<std::pair<uint64_t, uint64_t>> s;
+    for (uint32_t j = 0; j < n; j++) if (out_cap[j]) s.emplace_back(out_off[j], out_off[j] + out_cap[j]);
+    std::sort(s.begin(), s.end());
+    at = 0;
+    for (const auto& r : s) {
+        if (r.first > at) return false;
+        if (r.second > at) at = r.second;
+    }
+    return at == out_span;
+}
 // what the blocks produced and nothing else: block i's first min(out_len, out_cap) bytes at out_off[i], blocks that touch (in batch order)
 // as one range.  [first, second) byte ranges in batch order.  For the calls that promise the caller's bytes BETWEEN the slots without
 // staging the output buffer in (the decoders behind shared dictionaries): contiguous slots travel as one copy, slots with gaps one each.

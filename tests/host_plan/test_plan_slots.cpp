@@ -4,6 +4,8 @@
 //                            bytes the blocks produced and no byte between the slots
 //   test_plan_slots words    the words of rcx_plan_dict the decoders read (k_lz4_dict.hip, k_inflate_dict.hip): the clamped length, the
 //                            offset, the DICTID; the span that travels in
+//   test_plan_slots dense    rcx_plan_out_dense: the layouts whose used span may travel back in one copy, because every byte of it lies
+//                            in a slot
 // Prints HOST_PLAN_OK <section>.
 #include <stdio.h>
 #include <stdlib.h>
@@ -76,12 +78,55 @@ static void t_words()
     CHECK(!rcx_plan_dict(3, off.data(), len.data(), 65536, 65535, nullptr, "lz4 decode", p, err) && err.find("lz4 decode: block 2:") == 0);
 }
 
+static void t_dense()
+{
+    // fixed power-of-two slots in index order (bench.py, benchmarks/host_path_rate.py): dense
+    { V64 off, cap; for (uint64_t i = 0; i < 4096; i++) { off.push_back(65536 * i); cap.push_back(65536); }
+      CHECK(rcx_plan_out_dense(4096, off.data(), cap.data(), 65536 * 4096ull));
+      std::reverse(off.begin(), off.end());                                       // any order of the same slots
+      CHECK(rcx_plan_out_dense(4096, off.data(), cap.data(), 65536 * 4096ull));
+      off[7] += 1;                                                                // one byte of a gap (and one of overlap)
+      CHECK(!rcx_plan_out_dense(4096, off.data(), cap.data(), 65536 * 4096ull)); }
+    // a slot that does not start at 0; slots padded to 16; empty slots between full ones; no blocks; one empty block
+    { V64 off = {1}, cap = {10}; CHECK(!rcx_plan_out_dense(1, off.data(), cap.data(), 11)); }
+    { V64 off = {0, 16}, cap = {10, 10}; CHECK(!rcx_plan_out_dense(2, off.data(), cap.data(), 26)); }
+    { V64 off = {0, 999, 10, 3}, cap = {10, 0, 10, 0}; CHECK(rcx_plan_out_dense(4, off.data(), cap.data(), 20)); }
+    { CHECK(rcx_plan_out_dense(0, nullptr, nullptr, 0)); V64 off = {5}, cap = {0}; CHECK(rcx_plan_out_dense(1, off.data(), cap.data(), 5) == false); }
+    // a gap in index order that a later slot fills
+    { V64 off = {0, 20, 10}, cap = {10, 10, 10}; CHECK(rcx_plan_out_dense(3, off.data(), cap.data(), 30)); }
+    // random layouts against a map of the buffer: dense exactly when no byte of [0, out_span) is outside every slot
+    uint32_t seed = 777;
+    auto rnd = [&](uint32_t m) { seed = seed * 1664525u + 1013904223u; return (seed >> 8) % m; };
+    int ndense = 0;
+    for (int it = 0; it < 2000; it++) {
+        const uint32_t n = 1 + rnd(12);
+        V64 off(n), cap(n);
+        uint64_t at = rnd(3) ? 0 : rnd(3);
+        for (uint32_t i = 0; i < n; i++) {
+            if (!rnd(4)) at += rnd(3);                                            // sometimes a gap
+            else if (!rnd(6) && at) at -= 1;                                      // sometimes an overlap
+            off[i] = at; cap[i] = rnd(5) ? 1 + rnd(20) : 0; at += cap[i];
+        }
+        for (uint32_t i = n - 1; i > 0; i--) if (it & 1) { const uint32_t j = rnd(i + 1); std::swap(off[i], off[j]); std::swap(cap[i], cap[j]); }
+        rcx_spans sp; std::string err;
+        CHECK(rcx_plan_spans(n, off.data(), cap.data(), off.data(), cap.data(), sp, err));
+        std::vector<uint8_t> in_slot(sp.out_span + 1, 0);
+        for (uint32_t i = 0; i < n; i++) for (uint64_t k = 0; k < cap[i]; k++) in_slot[off[i] + k] = 1;
+        bool want = true;
+        for (uint64_t k = 0; k < sp.out_span; k++) want = want && in_slot[k];
+        CHECK(rcx_plan_out_dense(n, off.data(), cap.data(), sp.out_span) == want);
+        ndense += want;
+    }
+    CHECK(ndense > 100 && ndense < 1900);
+}
+
 int main(int argc, char** argv)
 {
     const std::string s = argc > 1 ? argv[1] : "";
     if (s == "copies") t_copies();
     else if (s == "words") t_words();
-    else { printf("usage: test_plan_slots copies|words\n"); return 2; }
+    else if (s == "dense") t_dense();
+    else { printf("usage: test_plan_slots copies|words|dense\n"); return 2; }
     printf("HOST_PLAN_OK %s\n", s.c_str());
     return 0;
 }

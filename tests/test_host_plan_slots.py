@@ -34,3 +34,9 @@ def test_the_words_the_decoders_read(exe):
     """The clamped length (LZ4: 65536 counts as 65535 and the offset moves with it), the offset's two words, the DICTIDs, the span that
     travels in; one byte over the limit is refused by the block's number behind the caller's prefix."""
     _run(exe, "words")
+
+
+def test_which_layouts_take_the_single_span_copy(exe):
+    """rcx_plan_out_dense: fixed slots that tile the buffer are dense in any order; a byte in front of the first slot, padding between
+    slots or a one-byte gap is not; 2000 random layouts (gaps, overlaps, empty slots, shuffled) against a byte map of the buffer."""
+    _run(exe, "dense")

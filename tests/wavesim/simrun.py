@@ -92,3 +92,25 @@ def run(codec, variant, blobs, caps, aux=None, n_out=None, in_misalign=0, out_mi
         mask[int(o):int(o) + int(c)] = False
     assert (out[mask] == 0xEE).all(), "kernel wrote outside its output slots"
     return outs, out_len, in_used, status, aux
+
+
+def run_layout(codec, variant, lay, aux=None, n_out=None, scratch_bytes=0, scratch_init=None):
+    """One launch on buffers and descriptors the caller laid out (tests/layout_cases.py: any offsets, any order, poison around the blocks).
+    lay: in_buf, in_off, in_len, out_off, out_cap, fresh_out(), n.  -> (output buffer, out_len, in_used, status, aux, the input buffer as
+    the launch left it).  No guard here: the caller's checks look at every byte of both buffers."""
+    n = lay.n
+    inb = lay.in_buf.copy()
+    out = lay.fresh_out()
+    off, lens = np.ascontiguousarray(lay.in_off, np.uint64), np.ascontiguousarray(lay.in_len, np.uint64)
+    ooff, ocap = np.ascontiguousarray(lay.out_off, np.uint64), np.ascontiguousarray(lay.out_cap, np.uint64)
+    out_len = np.zeros(n, np.uint64); in_used = np.zeros(n, np.uint64); status = np.full(n, -99, np.int32)
+    aux = np.zeros(max(n, 1), np.uint32) if aux is None else np.array(aux, np.uint32)
+    scratch = np.zeros(max(scratch_bytes, 8), np.uint8)
+    if scratch_init is not None:
+        scratch = np.frombuffer(bytes(scratch_init) + bytes(64), dtype=np.uint8).copy()
+    p = lambda a: a.ctypes.data
+    k = KArgs(p(inb), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), p(aux),
+              p(n_out) if n_out is not None else None, p(scratch), scratch.size, n)
+    rc = lib().sim_launch(codec, variant, C.byref(k))
+    assert rc == 0
+    return out, out_len, in_used, status, aux, inb
