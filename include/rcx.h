@@ -93,7 +93,13 @@ enum rcx_status {
     RCX_E_BZ2_DATA = 71,            /* a malformed block or stream structure */
     RCX_E_BZ2_BLOCK_CRC = 72,       /* a block's CRC does not match */
     RCX_E_BZ2_STREAM_CRC = 73,      /* a stream's combined CRC does not match */
-    RCX_E_BZ2_RANDOMISED = 74       /* the obsolete randomised bit is set (bzip2 has not written it since 0.9.5): not supported */
+    RCX_E_BZ2_RANDOMISED = 74,      /* the obsolete randomised bit is set (bzip2 has not written it since 0.9.5): not supported */
+    /* Zstandard files (extension, see rcx_zstd_decode_batch) */
+    RCX_E_ZSTD_MAGIC = 80,          /* the first 4 bytes are no frame */
+    RCX_E_ZSTD_HEADER = 81,         /* a reserved header bit, a window beyond 2^31 */
+    RCX_E_ZSTD_DATA = 82,           /* everything else the format calls corrupt */
+    RCX_E_ZSTD_CHECKSUM = 83,       /* the content checksum does not match */
+    RCX_E_ZSTD_DICT = 84            /* a Dictionary_ID: the frame needs a formatted dictionary, which the call does not take */
 };
 
 /* ---- batch-level return codes --------------------------------------------- */
@@ -541,6 +547,44 @@ int rcx_bzip2_decode_batch(rcx_ctx*, const rcx_batch*);
  *   not here   randomised blocks, more than one stream a file, rcx_launch_dev and rcx_multi_batch, which do not take RCX_BZIP2_ENCODE. */
 int rcx_bzip2_encode_batch(rcx_ctx*, const rcx_batch*, int level);
 
+/* ---- Zstandard (extension: the reference has no Zstandard) ----
+ * DECODE of .zst files as zstd / libzstd write them (RFC 8878).  Block i of the batch is one whole FILE: one or more concatenated frames
+ * (magic FD2FB528 little-endian), skippable frames (184D2A50..5F) skipped wherever they stand, optionally followed by other bytes; its
+ * decoded bytes go to its output slot.
+ *   dictionary dict_off / dict_len: both NULL, or a raw-content dictionary per file as a range anywhere in the input buffer (the
+ *              convention of rcx_lz4_decode_shared_batch; dict_len[i] = 0: none; files may share a range).  It is history in front of
+ *              EVERY frame of the file; repeat offsets start at 1, 4, 8.  A frame whose Dictionary_ID is not 0 needs a formatted
+ *              dictionary with entropy tables, which this call does not take: RCX_E_ZSTD_DICT.
+ *   results    success: RCX_OK, out_len[i] = the decoded size of all frames, in_used[i] = the byte just after the last accepted frame
+ *              (the file ends, after at least one frame, where the next four bytes are neither magic or fewer than four remain).
+ *              out_cap[i] too small, 0 included: RCX_E_OUTPUT_TOO_SMALL and out_len[i] = the exact size needed, so one retry
+ *              suffices -- the kernel goes on parsing and counting without storing, which also sizes a frame without
+ *              Frame_Content_Size; every structural check has been made by then, the content checksum, which needs the bytes, is
+ *              checked by the retry.  Any other failure: the first failure in stream order, out_len 0, in_used 0.  RCX_E_EOF: the
+ *              input ends inside a frame (also a file shorter than 4 bytes).  RCX_E_ZSTD_DATA: everything the format calls corrupt
+ *              that has no status of its own, among it a decoded size that is not the declared Frame_Content_Size and block type 3.
+ *              Nothing outside a file's own slot is written, a failing file affects no other, nothing below a slot is read.
+ *   oracle     bytes, out_len, in_used and accept / reject are libzstd 1.4.8's one-shot decoder's, also where it is laxer or stricter
+ *              than the RFC (a compressed block of fewer than 3 or of 128 KiB and more bytes is refused, a raw or RLE block is not held
+ *              to the window's block maximum, a resolved offset of 0 reads as 1, the reserved bits of the sequence modes are ignored, a count of 0 sequences
+ *              ends a block only when written in one byte: behind 80 00 the modes byte must follow and what follows it is not read).
+ *              Three departures: a sequence or weight bitstream that is read past its first bit is refused (libzstd goes on with
+ *              stale bits and may accept); Huffman codes longer than 11 bits are refused as the RFC asks (libzstd reads 12); four
+ *              literal streams for fewer than 6 literals of sizes 1, 2, 3 and 5 are refused (libzstd writes past its segments).
+ *   limits     a file and a slot below 4 GiB; at most 65535 files a call (more: RCX_RC_BAD_ARG).  RCX_MEM_HOST and RCX_MEM_DEVICE.
+ *              Synchronous.
+ *   stages     one wave per file, persistent over the files of a call, blocks in order: headers; the FSE and Huffman tables into
+ *              12 KiB of LDS; literals, a lane per Huffman stream, into a 128 KiB buffer of the context's scratch; sequences by one
+ *              lane into a ring of 64; execution by the wave, a lane per output byte of a batch, from three sources (literals, the
+ *              frame's output, the dictionary); XXH64
+ *              of a frame with a checksum.  DESIGN.md 3.22 has the kernel and what bounds it.
+ *   not here   the writer, formatted dictionaries, legacy (pre-0.8) frames, rcx_launch_dev and rcx_multi_batch, which do not take
+ *              RCX_ZSTD_DECODE or RCX_XXH64. */
+int rcx_zstd_decode_batch(rcx_ctx*, const rcx_batch*, const uint64_t* dict_off, const uint64_t* dict_len);
+/* XXH64 of every block, the twin of rcx_xxh32_batch: hash[i] = XXH64(block i, seed), eight bytes a hash; out_base, out_off, out_cap and
+ * out_len may be NULL.  A Zstandard frame's content checksum is the low 32 bits; the decoder above uses the same device code. */
+int rcx_xxh64_batch(rcx_ctx*, const rcx_batch*, uint64_t seed, uint64_t* hash);
+
 /* ---- device-resident descriptors (benchmark / pipeline use) ------------------ */
 /* Same kernels, but every array (offsets, lengths, status, ...) already lives
  * in HBM, nothing is copied and nothing is synchronised: the call enqueues on
@@ -580,8 +624,8 @@ enum rcx_codec {
 enum rcx_xcodec { RCX_XXH32 = 32, RCX_LZ4_DECODE_LINKED = 33, RCX_LZ4_ENCODE_HIST = 34, RCX_DEFLATE_ENCODE_HIST = 35, RCX_ZLIB_ENCODE_DICT = 36,
                   RCX_INFLATE_HIST = 37, RCX_ZLIB_DECODE_DICT = 38, RCX_LZ4_ENCODE_SHARED = 39, RCX_DEFLATE_ENCODE_SHARED = 40,
                   RCX_ZLIB_ENCODE_SHARED = 41, RCX_LZ4_DECODE_SHARED = 42, RCX_INFLATE_SHARED = 43, RCX_ZLIB_DECODE_SHARED = 44,
-                  RCX_DICT_TRAIN = 45, RCX_BZIP2_DECODE = 46, RCX_BZIP2_ENCODE = 47,
-                  RCX_XCODEC_END = 48 };
+                  RCX_DICT_TRAIN = 45, RCX_BZIP2_DECODE = 46, RCX_BZIP2_ENCODE = 47, RCX_ZSTD_DECODE = 48, RCX_XXH64 = 49,
+                  RCX_XCODEC_END = 50 };
 /* scratch bytes (HBM) the codec needs for nblocks blocks of <= max_block bytes.  Required for LZ4 encode, BWT and gzip
  * decode and the DEFLATE / zlib / gzip encoders; for RCX_INFLATE / RCX_ZLIB_DECODE it is what the default (wave-per-stream) decoder needs -- without it
  * rcx_launch_dev falls back to the lane-per-stream kernel (same results, slower on small batches). */

@@ -81,6 +81,11 @@ pub const RCX_E_BZ2_DATA: i32 = 71;
 pub const RCX_E_BZ2_BLOCK_CRC: i32 = 72;
 pub const RCX_E_BZ2_STREAM_CRC: i32 = 73;
 pub const RCX_E_BZ2_RANDOMISED: i32 = 74;
+pub const RCX_E_ZSTD_MAGIC: i32 = 80; // rcx_zstd_decode_batch: the first 4 bytes are no frame
+pub const RCX_E_ZSTD_HEADER: i32 = 81;
+pub const RCX_E_ZSTD_DATA: i32 = 82;
+pub const RCX_E_ZSTD_CHECKSUM: i32 = 83;
+pub const RCX_E_ZSTD_DICT: i32 = 84;
 // enum rcx_rc
 pub const RCX_RC_OK: c_int = 0;
 pub const RCX_RC_BAD_ARG: c_int = -1;
@@ -139,7 +144,9 @@ pub const RCX_ZLIB_DECODE_SHARED: c_int = 44;
 pub const RCX_DICT_TRAIN: c_int = 45;
 pub const RCX_BZIP2_DECODE: c_int = 46;
 pub const RCX_BZIP2_ENCODE: c_int = 47;
-pub const RCX_XCODEC_END: c_int = 48;
+pub const RCX_ZSTD_DECODE: c_int = 48;
+pub const RCX_XXH64: c_int = 49;
+pub const RCX_XCODEC_END: c_int = 50;
 
 #[link(name = "rcx")]
 extern "C" {
@@ -200,6 +207,9 @@ extern "C" {
     // ---- bzip2 (extension): block i is one whole .bz2 file, decoded to its slot
     pub fn rcx_bzip2_decode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch) -> c_int;
     pub fn rcx_bzip2_encode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, level: c_int) -> c_int;
+    // ---- Zstandard (extension): block i is one whole .zst file, decoded to its slot behind an optional raw-content dictionary; XXH64
+    pub fn rcx_zstd_decode_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, dict_off: *const u64, dict_len: *const u64) -> c_int;
+    pub fn rcx_xxh64_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, seed: u64, hash: *mut u64) -> c_int;
     // ---- BWT / MTF / DC (src/bwt/mod.rs, mtf.rs, dc.rs)
     pub fn rcx_bwt_forward_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;
     pub fn rcx_bwt_suffixes_batch(ctx: *mut rcx_ctx, b: *const rcx_batch, origin: *mut u32) -> c_int;

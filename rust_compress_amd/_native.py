@@ -27,6 +27,7 @@ E_EOF, E_OUTPUT_TOO_SMALL, E_MALFORMED = 1, 2, 3
 E_GZIP_MAGIC, E_GZIP_METHOD, E_GZIP_FLAGS, E_GZIP_CRC, E_GZIP_ISIZE = 50, 51, 52, 53, 54
 E_BWT_BLOCK_TOO_LARGE = 60
 E_BZ2_MAGIC, E_BZ2_DATA, E_BZ2_BLOCK_CRC, E_BZ2_STREAM_CRC, E_BZ2_RANDOMISED = 70, 71, 72, 73, 74
+E_ZSTD_MAGIC, E_ZSTD_HEADER, E_ZSTD_DATA, E_ZSTD_CHECKSUM, E_ZSTD_DICT = 80, 81, 82, 83, 84
 E_LZ4_MAGIC, E_LZ4_VERSION, E_LZ4_INPUT_TOO_LARGE, E_LZ4_HISTORY = 40, 41, 42, 43
 RC_OK, RC_BAD_ARG, RC_NO_DEVICE, RC_HIP_ERROR, RC_NO_MEMORY = 0, -1, -2, -3, -4
 
@@ -55,6 +56,7 @@ EXPORTS = [
     "rcx_lz4_decode_shared_batch", "rcx_inflate_shared_batch", "rcx_zlib_decode_shared_batch",
     "rcx_dict_train_batch", "rcx_dict_train_scratch_bytes",
     "rcx_bzip2_decode_batch", "rcx_bzip2_encode_batch",
+    "rcx_zstd_decode_batch", "rcx_xxh64_batch",
 ]
 
 
@@ -146,6 +148,8 @@ def lib():
         L.rcx_dict_train_scratch_bytes.restype = C.c_uint64
         L.rcx_bzip2_decode_batch.argtypes = [C.c_void_p, C.POINTER(Batch)]
         L.rcx_bzip2_encode_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int]
+        L.rcx_zstd_decode_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p]
+        L.rcx_xxh64_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_uint64, C.c_void_p]
         L.rcx_deflate_level_scratch_bytes.argtypes = [C.c_uint32, C.c_uint64]
         L.rcx_deflate_level_scratch_bytes.restype = C.c_uint64
         for name in ("rcx_inflate_batch", "rcx_zlib_decode_batch", "rcx_adler32_batch", "rcx_crc32_batch",

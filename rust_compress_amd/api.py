@@ -429,6 +429,34 @@ class Context:
         res.outputs = [o if st == 0 else b"" for o, st in zip(res.outputs, res.status)]
         return res
 
+    def zstd_decode(self, blobs, caps, dictionary=None):
+        """One whole .zst file per blob (rcx_zstd_decode_batch; extension): one or more concatenated frames, skippable frames skipped,
+        optionally followed by other bytes.  dictionary (bytes for all blobs, or a list with one entry, bytes or None, per blob): raw
+        content, history in front of every frame; equal dictionaries lie in the input buffer once.  status RCX_OK: outputs[i] the
+        decoded bytes, in_used[i] the byte just after the last frame.  A cap too small gives E_OUTPUT_TOO_SMALL and out_len[i] = the
+        exact size (caps of 0: a size query); any other failure the first one in stream order (E_ZSTD_*, E_EOF) with out_len 0.
+        zstd.decode_many does the two calls."""
+        if dictionary is None:
+            base, off, lens = B.pack(blobs)
+            d_off = d_len = None
+        else:
+            base, off, lens, d_off, d_len, _ = _pack_shared(blobs, dictionary, 1 << 32)
+        res = self._shared_decode("rcx_zstd_decode_batch", base, off, lens, d_off, d_len, caps)
+        res.outputs = [o if st == 0 else b"" for o, st in zip(res.outputs, res.status)]     # (out_len of a slot too small is a size, not bytes)
+        return res
+
+    def xxh64(self, blobs, seed=0):
+        """XXH64 of every blob (rcx_xxh64_batch; extension) -> a uint64 array.  A Zstandard frame's content checksum is the low 32 bits."""
+        n = len(blobs)
+        base, off, lens = B.pack(blobs)
+        status = np.zeros(max(n, 1), np.int32)
+        in_used = np.zeros(max(n, 1), np.uint64)
+        hashes = np.zeros(max(n, 1), np.uint64)
+        p = lambda a: a.ctypes.data
+        b = N.Batch(p(base), p(off), p(lens), None, None, None, None, p(in_used), p(status), n, N.MEM_HOST)
+        self._chk(N.lib().rcx_xxh64_batch(self._h, C.byref(b), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_void_p(p(hashes))))
+        return hashes[:n]
+
     def _deflate_encode(self, fn, blobs, caps, framing, level):
         caps = caps if caps is not None else [deflate_bound(len(b)) + framing for b in blobs]
         if level == 1:

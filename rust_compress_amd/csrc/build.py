@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-TUS = ["rcx_api", "tu_lz4", "tu_inflate", "tu_bwt", "tu_serial", "tu_deflate_encode", "tu_lz4_hc", "tu_lz4_frame", "tu_dict_train", "tu_bzip2", "tu_bzip2_enc"]
+TUS = ["rcx_api", "tu_lz4", "tu_inflate", "tu_bwt", "tu_serial", "tu_deflate_encode", "tu_lz4_hc", "tu_lz4_frame", "tu_dict_train", "tu_bzip2", "tu_bzip2_enc", "tu_zstd"]
 
 
 def _out(ab):

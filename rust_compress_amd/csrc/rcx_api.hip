@@ -150,6 +150,11 @@ extern "C" const char* rcx_status_string(int s)
     case RCX_E_BZ2_BLOCK_CRC: return "invalid CRC on bzip2 block";
     case RCX_E_BZ2_STREAM_CRC: return "invalid combined CRC on bzip2 stream";
     case RCX_E_BZ2_RANDOMISED: return "randomised bzip2 block (not supported)";
+    case RCX_E_ZSTD_MAGIC: return "not a zstd frame";
+    case RCX_E_ZSTD_HEADER: return "unsupported zstd frame header";
+    case RCX_E_ZSTD_DATA: return "invalid zstd data";
+    case RCX_E_ZSTD_CHECKSUM: return "invalid content checksum on zstd frame";
+    case RCX_E_ZSTD_DICT: return "zstd frame needs a formatted dictionary (not supported)";
     default: return "unknown status";
     }
 }
@@ -224,6 +229,8 @@ struct rcx_call {
     uint64_t dict_span;                  // shared dictionaries: one past their highest byte in the input buffer (it travels in with the blocks)
     const rcx_train_plan* train;         // dictionary training: the plan of the call (its words are aux_in), else null
     const rcx_batch* bz2;                // bzip2 decode and encode: the caller's batch (its host arrays steer the stages), else null
+    uint64_t seed64;                     // XXH64
+    const rcx_zstd_plan* zstd;           // Zstandard decode: the plan of the call (its dictionary words are aux_in), else null
 };
 
 // ---- per-codec traits of the host path ------------------------------------------------------------------------------------------------
@@ -236,6 +243,7 @@ enum scratch_rule { SCRATCH_BY_CODEC,                                  // rcx_sc
                     SCRATCH_HC_DICT_SEGS, SCRATCH_DEFLATE_DICT_SEGS,   // the real segments and the distinct dictionaries
                     SCRATCH_TRAIN,                                     // dictionary training: what the call's plan carved
                     SCRATCH_NONE,                                      // bzip2 decode: the launch reserves d_scratch itself
+                    SCRATCH_ZSTD,                                      // Zstandard decode: a literal buffer per wave, by the call's plan
                     SCRATCH_DC_OPTIONAL };                             // chunk states: none with contexts, and none when they cannot be had
 enum back_policy { BACK_USED_SPAN, BACK_INFLATE /* mirrored: the streams the first pass handed back */, BACK_CHAINS, BACK_SLOTS /* what the blocks produced, range by range */ };
 struct codec_traits {
@@ -279,16 +287,18 @@ static codec_traits traits_of(int codec, uint32_t param)
     case RCX_BZIP2_DECODE: t.back = BACK_SLOTS; t.scratch = SCRATCH_NONE; break;
     // ... and written: a slot holds its stream or, too small, nothing; the launch reserves its three buffers itself
     case RCX_BZIP2_ENCODE: t.back = BACK_SLOTS; t.scratch = SCRATCH_NONE; break;
+    // .zst files: as bzip2's, a slot is written up to what the file decoded to and out_len of a slot too small is a size
+    case RCX_ZSTD_DECODE: t.back = BACK_SLOTS; t.scratch = SCRATCH_ZSTD; break;
     case RCX_DC_ENCODE: t.scratch = SCRATCH_DC_OPTIONAL; break;
     case RCX_LZ4_DECODE_LINKED: t.back = BACK_CHAINS; break;
-    case RCX_ADLER32: case RCX_CRC32: case RCX_XXH32: t.needs_out = false; break;
+    case RCX_ADLER32: case RCX_CRC32: case RCX_XXH32: case RCX_XXH64: t.needs_out = false; break;
     default: break;
     }
     return t;
 }
 static rcx_call call_of(int codec, uint32_t param = 0, const uint32_t* aux_in = nullptr, uint32_t* aux_out = nullptr, const uint64_t* n_out = nullptr)
 {
-    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr, 0, 1, 0, nullptr, nullptr};
+    return {codec, param, aux_in, aux_out, n_out, traits_of(codec, param).needs_out, 0, nullptr, 0, 1, 0, nullptr, nullptr, 0, nullptr};
 }
 
 // ---- kernel arguments: built here and nowhere else ---------------------------------------------------------------------------------------
@@ -418,6 +428,14 @@ static int launch_codec(rcx_ctx* c, const rcx_call& call, rcx_kargs& k)
     case RCX_XXH32:
         rcx_tu_xxh32(s, k, call.seed);
         break;
+    case RCX_XXH64:
+        rcx_tu_xxh64(s, k, call.seed64);
+        break;
+    case RCX_ZSTD_DECODE: {                                      // k.aux: the words of rcx_plan_dict, never null
+        if (!call.zstd || !call.aux_in) { c->err = "zstd decode: use rcx_zstd_decode_batch"; return RCX_RC_BAD_ARG; }
+        int rc = rcx_tu_zstd_decode(s, k, call.zstd->waves, v, c->err);
+        if (rc) return rc;
+        break; }
     case RCX_LZ4_DECODE_LINKED:
         if (!call.link) { c->err = "lz4 linked decode: use rcx_lz4_decode_linked_batch"; return RCX_RC_BAD_ARG; }
         rcx_tu_lz4_decode_linked(s, k, call.link->order, call.link->plan->rounds_off.data(), call.link->plan->nrounds, call.link->head,
@@ -677,6 +695,7 @@ static int reserve_scratch(rcx_ctx* c, const rcx_call& call, batch_state& st)
         sb = rcx_tu_deflate_dict_scratch(n, segs, call.nhist);
         break;
     case SCRATCH_TRAIN: sb = call.train ? call.train->scratch_bytes : 0; break;
+    case SCRATCH_ZSTD: sb = call.zstd ? call.zstd->scratch_bytes : 0; break;
     case SCRATCH_NONE: return RCX_RC_OK;
     case SCRATCH_DC_OPTIONAL:                                       // withctx: the wave-per-block kernel encodes, no chunk states
         sb = call.param ? 0 : rcx_scratch_bytes(call.codec, n, st.sp.max_block);
@@ -833,9 +852,9 @@ static int copy_back(rcx_ctx* c, const rcx_call& call, batch_state& st)
                 HIPCHK(c, hipMemcpyAsync(b->out_base + r.first, st.d_out + r.first, r.second - r.first, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         } else if (st.t.back == BACK_SLOTS) {
-            // (bzip2: out_len of a file that did not fit is the size it needs; its slot holds nothing to deliver)
+            // (bzip2, zstd: out_len of a file that did not fit is the size it needs; its slot holds nothing to deliver)
             std::vector<uint64_t> made;
-            if (call.codec == RCX_BZIP2_DECODE || call.codec == RCX_BZIP2_ENCODE) {
+            if (call.codec == RCX_BZIP2_DECODE || call.codec == RCX_BZIP2_ENCODE || call.codec == RCX_ZSTD_DECODE) {
                 made.assign(st.out_len(), st.out_len() + N);
                 for (size_t i = 0; i < N; i++) if (st.h_status[i] == RCX_E_OUTPUT_TOO_SMALL) made[i] = 0;
             }
@@ -1107,6 +1126,30 @@ extern "C" int rcx_bzip2_encode_batch(rcx_ctx* c, const rcx_batch* b, int level)
     rcx_call call = call_of(RCX_BZIP2_ENCODE, (uint32_t)level);
     call.bz2 = b;
     return run_batch(c, call, b);
+}
+// .zst files: block i is one whole file, one persistent wave each (k_zstd.hip).  rcx_plan_zstd checks the arguments, lays the dictionary
+// words out and sizes the scratch; the span of the dictionaries' ranges widens what travels in from host memory.
+extern "C" int rcx_zstd_decode_batch(rcx_ctx* c, const rcx_batch* b, const uint64_t* dict_off, const uint64_t* dict_len)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    rcx_call call = call_of(RCX_ZSTD_DECODE);
+    if (!b || !b->nblocks) return run_batch(c, call, b);
+    rcx_zstd_plan plan;
+    if (!rcx_plan_zstd(b->nblocks, dict_off, dict_len, plan, c->err)) return RCX_RC_BAD_ARG;
+    call.aux_in = plan.dict.aux.data(); call.aux_words = RCX_DICT_WORDS; call.dict_span = plan.dict.span; call.zstd = &plan;
+    return run_batch(c, call, b);                                // (waits for the stream: the plan above may go)
+}
+// XXH64 of every block.  The kernel leaves a hash in the descriptors' 64-bit result word, out_len: the caller's array stands in for it.
+extern "C" int rcx_xxh64_batch(rcx_ctx* c, const rcx_batch* b, uint64_t seed, uint64_t* hash)
+{
+    if (!c) return RCX_RC_BAD_ARG;
+    if (b && b->nblocks && !hash) { c->err = "xxh64: null hash array"; return RCX_RC_BAD_ARG; }
+    rcx_call call = call_of(RCX_XXH64);
+    call.seed64 = seed;
+    if (!b) return run_batch(c, call, b);
+    rcx_batch bb = *b;
+    bb.out_len = hash;
+    return run_batch(c, call, &bb);
 }
 extern "C" uint64_t rcx_dict_train_scratch_bytes(uint32_t njobs, uint64_t max_corpus, uint64_t max_cap, uint32_t k, uint32_t f)
 {

@@ -578,3 +578,39 @@ inline uint64_t rcx_plan_bz2e_block_bound(uint32_t n)
     const uint64_t bits = 17 * nsym + 6 * nsel + 6ull * (5 + 258 * 33) + 48 + 32 + 1 + 24 + 16 + 256 + 3 + 15;
     return ((bits + 31) / 32) * 4 + 16;
 }
+
+// ---- Zstandard decode (rcx_zstd_decode_batch, k_zstd.hip) ---------------------------------------------------------
+// One persistent wave per file, RCX_ZSTD_MAX_WAVES at the most, each with a buffer for one block's literals in the scratch.  The
+// dictionaries are raw content, ranges anywhere in the input buffer: rcx_plan_dict's words with the lengths unclamped (an offset reaches
+// as far as the frame's own output and the dictionary go); both arrays null: no file has one, and the words say so.
+// Pure host code (tests/host_plan/test_plan_zstd.cpp).
+#define RCX_ZSTD_MAX_FILES 65535u
+#define RCX_ZSTD_MAX_WAVES 2048u
+#define RCX_ZSTD_LIT_SLOT (131072u + 64u)
+struct rcx_zstd_plan {
+    rcx_dict_plan dict;                       // aux: RCX_DICT_WORDS a file
+    uint32_t waves = 0;
+    uint64_t scratch_bytes = 0;
+};
+// false: `err` names what is wrong.  n > 0.
+inline bool rcx_plan_zstd(uint32_t n, const uint64_t* dict_off, const uint64_t* dict_len, rcx_zstd_plan& p, std::string& err)
+{
+    p = rcx_zstd_plan();
+    if (n > RCX_ZSTD_MAX_FILES) { err = "zstd decode: at most 65535 files a call"; return false; }
+    if (!dict_off != !dict_len) { err = "zstd decode: dict_off and dict_len come together or not at all"; return false; }
+    const std::vector<uint64_t> none(dict_len ? 0 : n, 0);
+    if (!rcx_plan_dict(n, dict_len ? dict_off : none.data(), dict_len ? dict_len : none.data(), 0xffffffffull, 0xffffffffull, nullptr,
+                       "zstd decode", p.dict, err))
+        return false;
+    p.waves = n < RCX_ZSTD_MAX_WAVES ? n : RCX_ZSTD_MAX_WAVES;
+    p.scratch_bytes = (uint64_t)p.waves * RCX_ZSTD_LIT_SLOT;
+    return true;
+}
+// The size query and the retry: the files of a first call that must be decoded again, with the capacity each one asked for.  A file that
+// reported RCX_E_OUTPUT_TOO_SMALL names its exact size in out_len; every other file is final.
+inline std::vector<std::pair<uint32_t, uint64_t>> rcx_plan_zstd_retry(uint32_t n, const int32_t* status, const uint64_t* out_len)
+{
+    std::vector<std::pair<uint32_t, uint64_t>> r;
+    for (uint32_t i = 0; i < n; i++) if (status[i] == RCX_E_OUTPUT_TOO_SMALL) r.emplace_back(i, out_len[i]);
+    return r;
+}

@@ -76,6 +76,10 @@ int rcx_tu_dict_train(hipStream_t s, rcx_kargs& k, const rcx_train_plan& plan, s
 struct rcx_bz2_alloc;                        // rcx_plan.h
 int rcx_tu_bzip2_decode(hipStream_t s, rcx_kargs& k, const uint64_t* h_in_len, const uint64_t* h_out_off, const uint64_t* h_out_cap,
                         const rcx_bz2_alloc& alloc, uint32_t round, std::string& err);          // round: candidates a round, 0 = the default
+// tu_zstd.hip: XXH64 of every block (the hash comes back in out_len); .zst files (k_zstd.hip), one persistent wave per file up to `waves`
+// (rcx_plan_zstd), k.aux = the words of rcx_plan_dict, k.scratch = a literal buffer per wave
+void rcx_tu_xxh64(hipStream_t s, rcx_kargs& k, uint64_t seed);
+int rcx_tu_zstd_decode(hipStream_t s, rcx_kargs& k, uint32_t waves, int variant, std::string& err);
 // tu_bzip2_enc.hip: whole files to .bz2 streams (k_bzip2_enc.hip).  Synchronous: it reads the chunks' lengths and the blocks' records
 // back and asks `alloc` for three buffers (0: the stages', 1: the sort's, 2: what lasts for the call).  Calls rcx_tu_bwt_forward.
 int rcx_tu_bzip2_encode(hipStream_t s, rcx_kargs& k, const uint64_t* h_in_off, const uint64_t* h_in_len, const uint64_t* h_out_off,

@@ -1,0 +1,215 @@
+"""GPU suite of the Zstandard decoder (rcx_zstd_decode_batch; k_zstd.hip) and of rcx_xxh64_batch: about 64 mixed files in one call
+against tests/zstd_ref.py, from host and from device memory and twice; the size query and the exact retry with guard bytes; the
+device's results against the wave simulator's; the 200 single-bit flips; dictionaries, one shared by 64 records; XXH64 against plain
+Python; the Python layer; free layouts."""
+import ctypes as C
+import io
+
+import numpy as np
+import pytest
+
+import layout_cases as LC
+import sim_zstd_run as S
+import zstd_cases as Z
+import zstd_ref as R
+from rust_compress_amd import _native as N
+from rust_compress_amd import zstd
+
+pytestmark = pytest.mark.gpu
+TOO_SMALL = R.STATUS["E_OUTPUT_TOO_SMALL"]
+
+
+def _p(a):
+    return a.ctypes.data if a is not None else None
+
+
+def raw_call(ctx, inb, in_off, in_len, d_off, d_len, out, out_off, out_cap, device=False):
+    n = len(in_off)
+    out_len, in_used, status = np.full(n, 0x7777, np.uint64), np.full(n, 0x7777, np.uint64), np.full(n, -99, np.int32)
+    if device:
+        import torch
+        t_in, t_out = torch.from_numpy(inb).cuda(), torch.from_numpy(out).cuda()
+        b = N.Batch(t_in.data_ptr(), _p(in_off), _p(in_len), t_out.data_ptr(), _p(out_off), _p(out_cap), _p(out_len), _p(in_used), _p(status), n, N.MEM_DEVICE)
+    else:
+        b = N.Batch(_p(inb), _p(in_off), _p(in_len), _p(out), _p(out_off), _p(out_cap), _p(out_len), _p(in_used), _p(status), n, N.MEM_HOST)
+    rc = N.lib().rcx_zstd_decode_batch(ctx._h, C.byref(b), C.c_void_p(_p(d_off)), C.c_void_p(_p(d_len)))
+    assert rc == N.RC_OK, (rc, N.lib().rcx_last_error(ctx._h).decode())
+    in_after = inb
+    if device:
+        out, in_after = t_out.cpu().numpy(), t_in.cpu().numpy()
+    return out, out_len, in_used, status, in_after
+
+
+def call(ctx, cases, caps, device=False):
+    """one rcx_zstd_decode_batch over the layout of sim_zstd_run.layout -> results in the form of sim_zstd_run.run's"""
+    dicts = [c["dict"] for c in cases]
+    inb, in_off, in_len, d_off, d_len, out, out_off, out_cap = S.layout([c["blob"] for c in cases], caps, dicts if any(dicts) else None)
+    out, out_len, in_used, status, _ = raw_call(ctx, inb, in_off, in_len, d_off, d_len, out, out_off, out_cap, device)
+    data = [bytes(out[int(out_off[i]):int(out_off[i]) + int(out_len[i])]) if status[i] == 0 else None for i in range(len(cases))]
+    return dict(status=status, out_len=out_len, in_used=in_used, out=out, out_off=out_off, out_cap=out_cap, data=data)
+
+
+def check(cases, r, caps):
+    for i, c in enumerate(cases):
+        st, data, out_len, used = R.outcome(c["blob"], c["dict"] or b"", caps[i])
+        got = (int(r["status"][i]), int(r["out_len"][i]), int(r["in_used"][i]))
+        assert got == (R.STATUS[st], out_len, used), (c["name"], got, st, out_len, used)
+        if st == "OK":
+            assert r["data"][i] == data, c["name"]
+    assert S.untouched_outside(r["out"], r["out_off"], r["out_cap"])
+
+
+def same(a, b):
+    return (list(a["status"]) == list(b["status"]) and list(a["out_len"]) == list(b["out_len"]) and list(a["in_used"]) == list(b["in_used"])
+            and a["data"] == b["data"])
+
+
+def _slot(c):
+    e = Z.expected(c["blob"], c["dict"])
+    return e[2] if e[0] == "OK" else 64
+
+
+@pytest.fixture(scope="module")
+def mixed():
+    cases = Z.mixed64()
+    assert 56 <= len(cases) <= 72
+    return cases, [_slot(c) for c in cases]
+
+
+@pytest.fixture(scope="module")
+def mixed_host(ctx, mixed):
+    return call(ctx, mixed[0], mixed[1])
+
+
+def test_mixed64_from_host_memory(mixed, mixed_host):
+    cases, caps = mixed
+    check(cases, mixed_host, caps)
+    sts = set(int(s) for s in mixed_host["status"])
+    assert {0, 1, 80, 81, 82, 83, 84} <= sts
+
+
+def test_mixed64_from_device_memory_and_again(ctx, mixed, mixed_host):
+    cases, caps = mixed
+    dev = call(ctx, cases, caps, device=True)
+    check(cases, dev, caps)
+    assert same(dev, mixed_host)
+    assert same(call(ctx, cases, caps), mixed_host)
+
+
+def test_size_query_then_retry_into_exact_slots(ctx, mixed):
+    cases, _ = mixed
+    zero = [0] * len(cases)
+    q = call(ctx, cases, zero)
+    check(cases, q, zero)
+    sized = [i for i in range(len(cases)) if int(q["status"][i]) == TOO_SMALL]
+    assert any(cases[i]["name"] == "stream_no_size" for i in sized)
+    again, caps = [cases[i] for i in sized], [int(q["out_len"][i]) for i in sized]
+    r = call(ctx, again, caps, device=True)
+    check(again, r, caps)
+    assert all(int(s) in (0, 83) for s in r["status"])            # what the size query could not check is the content checksum alone
+
+
+def test_results_equal_the_simulators_below_4_kib(ctx, mixed):
+    cases = [c for c in mixed[0] if len(c["blob"]) < 4096]
+    caps = [_slot(c) for c in cases]
+    sim = S.run([c["blob"] for c in cases], caps, [c["dict"] for c in cases] if any(c["dict"] for c in cases) else None)
+    assert sim["rc"] == 0 and same(call(ctx, cases, caps), sim)
+
+
+def test_single_bit_flips_in_one_call(ctx):
+    cases = [dict(name=f["name"], blob=f["blob"], dict=None) for f in Z.flips()]
+    assert len(cases) >= 196
+    caps = [max(Z.expected(c["blob"])[2], 16) for c in cases]
+    check(cases, call(ctx, cases, caps), caps)
+
+
+def test_dictionary_record_with_and_without(ctx):
+    g = [g for g in Z.golden() if g["dict"]][0]
+    cases = [dict(name="with", blob=g["blob"], dict=g["dict"]), dict(name="without", blob=g["blob"], dict=None)]
+    caps = [len(g["raw"])] * 2
+    r = call(ctx, cases, caps)
+    check(cases, r, caps)
+    assert r["data"][0] == g["raw"] and int(r["status"][1]) == R.STATUS["E_ZSTD_DATA"]       # the offset beyond history
+    plain = call(ctx, [dict(name="none", blob=g["blob"], dict=None)], caps[:1])                  # both arrays NULL
+    assert int(plain["status"][0]) == R.STATUS["E_ZSTD_DATA"]
+
+
+def test_one_dictionary_shared_by_64_records(ctx):
+    g = [g for g in Z.golden() if g["dict"]][0]
+    cases = [dict(name="record%d" % i, blob=g["blob"], dict=g["dict"]) for i in range(64)]
+    caps = [len(g["raw"])] * 64
+    for device in (False, True):
+        r = call(ctx, cases, caps, device)
+        assert all(int(s) == 0 for s in r["status"]) and all(d == g["raw"] for d in r["data"])
+        assert S.untouched_outside(r["out"], r["out_off"], r["out_cap"])
+
+
+def test_xxh64_against_plain_python(ctx):
+    rng = np.random.default_rng(64)
+    blobs = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (0, 1, 31, 32, 33, 65536)]
+    for seed in (0, 0x9E3779B97F4A7C15):
+        assert [int(h) for h in ctx.xxh64(blobs, seed)] == [R.xxh64(b, seed) for b in blobs]
+    # misaligned offsets: the blocks 1, 2, 3, 5 and 7 bytes into one buffer
+    buf = rng.integers(0, 256, 70000, dtype=np.uint8)
+    off = np.array([1, 2, 3, 5, 7, 4099], np.uint64)
+    lens = np.array([65536, 33, 32, 31, 1, 0], np.uint64)
+    status, in_used, hashes = np.full(6, -9, np.int32), np.zeros(6, np.uint64), np.zeros(6, np.uint64)
+    b = N.Batch(_p(buf), _p(off), _p(lens), None, None, None, None, _p(in_used), _p(status), 6, N.MEM_HOST)
+    assert N.lib().rcx_xxh64_batch(ctx._h, C.byref(b), C.c_uint64(5), C.c_void_p(_p(hashes))) == N.RC_OK
+    assert [int(h) for h in hashes] == [R.xxh64(buf[int(o):int(o) + int(l)].tobytes(), 5) for o, l in zip(off, lens)]
+    assert list(status) == [0] * 6 and list(in_used) == list(lens)
+
+
+def test_decode_many_with_return_exceptions(ctx, mixed):
+    cases = [c for c in mixed[0] if c["dict"] is None][:40]
+    res = zstd.decode_many([c["blob"] for c in cases], ctx=ctx, return_exceptions=True)
+    kinds = {"E_EOF": zstd.TruncatedError, "E_ZSTD_MAGIC": zstd.MagicError, "E_ZSTD_HEADER": zstd.HeaderError, "E_ZSTD_DATA": zstd.DataError,
+             "E_ZSTD_CHECKSUM": zstd.ChecksumError, "E_ZSTD_DICT": zstd.DictionaryError}
+    for c, r in zip(cases, res):
+        st, data = Z.expected(c["blob"])[:2]
+        if st == "OK":
+            assert r == data, c["name"]
+        else:
+            assert type(r) is kinds[st] and r.status == R.STATUS[st], (c["name"], r)
+    with pytest.raises(zstd.FilesFailed):
+        zstd.decode_many([c["blob"] for c in cases], ctx=ctx)
+    g = [g for g in Z.golden() if g["dict"]][0]
+    assert zstd.decode_many([g["blob"], g["blob"]], dictionary=g["dict"], ctx=ctx) == [g["raw"]] * 2
+    assert zstd.declared_size(g["blob"]) == len(g["raw"])
+    assert zstd.declared_size([x for x in Z.golden() if x["name"] == "stream_no_size"][0]["blob"]) is None
+
+
+def test_decoder_hands_trailing_bytes_back(ctx):
+    g = [g for g in Z.golden() if g["name"] == "text_5000_l3"][0]
+    h = [g for g in Z.golden() if g["name"] == "stream_no_size"][0]
+    r = io.BytesIO(g["blob"] + h["blob"] + b"behind the last frame")
+    d = zstd.Decoder(r)
+    assert d.read(100) == g["raw"][:100] and not d.eof()
+    assert d.read_to_end() == g["raw"][100:] + h["raw"] and d.eof()
+    assert d.finish().read() == b"behind the last frame"
+    with pytest.raises(zstd.TruncatedError):
+        zstd.Decoder(io.BytesIO(g["blob"][:-5])).read()
+
+
+def test_free_layouts_nothing_outside_the_slots_nothing_below_them(ctx):
+    """tests/layout_cases.py's layouts (packed from offset 0, every residue behind random gaps, shuffled) with both poisons, from host and
+    from device memory: the reference's results, the poison everywhere outside the slots, the input untouched, nothing depends on what
+    lies around the slots"""
+    cases = [c for c in Z.mixed64() if c["dict"] is None and len(c["blob"]) < 20000][:36]
+    blocks = [c["blob"] for c in cases]
+    caps = [_slot(c) for c in cases]
+    wants = []
+    for c, cap in zip(cases, caps):
+        st, data, out_len, used = R.outcome(c["blob"], b"", cap)
+        wants.append(LC.Want(R.STATUS[st], data=data, in_used=used, out_len=out_len))
+    for name in LC.layout_names():
+        for device in (False, True):
+            got = {}
+            for poison in LC.POISONS:
+                lay = LC.build(name, blocks, caps, poison)
+                out, out_len, in_used, status, in_after = raw_call(ctx, lay.in_buf.copy(), lay.in_off, lay.in_len, None, None, lay.fresh_out(),
+                                                                   lay.out_off, lay.out_cap, device)
+                got[poison] = (lay, LC.Got(out, out_len, in_used, status, None, in_after))
+                LC.check_all(lay, got[poison][1], wants, tag="zstd %s" % ("device" if device else "host"))
+            (la, ga), (lb, gb) = got[LC.POISONS[0]], got[LC.POISONS[1]]
+            LC.check_same(la, ga, lb, gb, wants, tag="zstd")
