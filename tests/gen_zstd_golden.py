@@ -1,7 +1,8 @@
 """Writes tests/golden/zstd/*.zst and manifest.json.  Run once by hand where ctypes finds libzstd.so.1 (1.4.8 wrote the committed
 files): python tests/gen_zstd_golden.py.  The raw inputs are recipes (tests/zstd_cases.raw_of), not files; every frame stays under
 100 KiB.  Each entry names what its frame must reach (`needs`, the words of zstd_cases.props); the generator decodes what it wrote
-with tests/zstd_ref.py and asserts them, so that another library version cannot silently lose a path."""
+with tests/zstd_ref.py and asserts them, so that another library version cannot silently lose a path.  FRAMES are the manifest's
+"frames" (zstd_cases.golden()), MORE its "more" (zstd_cases.golden_more())."""
 import ctypes as C
 import json
 import os
@@ -80,14 +81,17 @@ FRAMES = [
     ("stream_no_size", T(6000, 3), {"stream": True}, ["fcs0", "window"]),
     ("record_behind_dictionary", T(2048, 9), {"dict": T(32768, 1)}, ["dict"]),
 ]
+# written to the manifest's "more" (zstd_cases.golden_more()): libzstd alone writes Huffman streams, so the literals header of 5 bytes
+# and a literals section that fills a block need frames of its making
+MORE = [
+    ("rand200_20000_l3", ["randmod", 20000, 7, 200], {}, ["hufhdr5"]),
+    ("rand48_131072_l1", ["randmod", 131072, 7, 48], {"level": 1}, ["hufhdr5", "lit_full"]),
+]
 
 
-def main():
-    z = lib()
-    print("libzstd", z.ZSTD_versionString().decode())
-    os.makedirs(cases.GOLDEN, exist_ok=True)
+def write(z, entries):
     frames = []
-    for name, recipe, args, needs in FRAMES:
+    for name, recipe, args, needs in entries:
         raw = cases.raw_of(recipe)
         args = dict(args)
         drecipe = args.pop("dict", None)
@@ -110,8 +114,16 @@ def main():
             e["dict"] = drecipe
         frames.append(e)
         print("%-28s %7d -> %6d  %s" % (name, len(raw), len(blob), " ".join(needs)))
+    return frames
+
+
+def main():
+    z = lib()
+    print("libzstd", z.ZSTD_versionString().decode())
+    os.makedirs(cases.GOLDEN, exist_ok=True)
+    frames, more = write(z, FRAMES), write(z, MORE)
     with open(os.path.join(cases.GOLDEN, "manifest.json"), "w") as fh:
-        json.dump({"libzstd": z.ZSTD_versionString().decode(), "frames": frames}, fh, indent=1)
+        json.dump({"libzstd": z.ZSTD_versionString().decode(), "frames": frames, "more": more}, fh, indent=1)
         fh.write("\n")
 
 

@@ -26,6 +26,8 @@ static void plan()
     std::vector<uint64_t> off(5000, 0), len(5000, 0);
     CHECK(rcx_plan_zstd(5000, nullptr, nullptr, p, err));
     CHECK(p.waves == RCX_ZSTD_MAX_WAVES && p.scratch_bytes == (uint64_t)RCX_ZSTD_MAX_WAVES * RCX_ZSTD_LIT_SLOT);
+    // tests/test_gpu_zstd.py's 4160 files: every wave takes two, 64 of them three
+    CHECK(rcx_plan_zstd(4160, nullptr, nullptr, p, err) && p.waves == 2048 && 4160 == 2 * p.waves + 64);
     // one range shared by many files, one file with none, one with a dictionary of 1 MiB beyond 4 GiB: nothing is clamped
     for (uint32_t i = 0; i < 5000; i++) { off[i] = 64; len[i] = 32768; }
     len[7] = 0; off[7] = 0xdeadbeef;

@@ -1,7 +1,8 @@
 """GPU suite of the Zstandard decoder (rcx_zstd_decode_batch; k_zstd.hip) and of rcx_xxh64_batch: about 64 mixed files in one call
 against tests/zstd_ref.py, from host and from device memory and twice; the size query and the exact retry with guard bytes; the
 device's results against the wave simulator's; the 200 single-bit flips; dictionaries, one shared by 64 records; XXH64 against plain
-Python; the Python layer; free layouts."""
+Python; the Python layer; free layouts; the edge cases of zstd_cases.edge_cases() and golden_more(); the capacity sweep; 4160 files on
+the call's 2048 persistent waves; the 600 mutations."""
 import ctypes as C
 import io
 
@@ -213,3 +214,86 @@ def test_free_layouts_nothing_outside_the_slots_nothing_below_them(ctx):
                 LC.check_all(lay, got[poison][1], wants, tag="zstd %s" % ("device" if device else "host"))
             (la, ga), (lb, gb) = got[LC.POISONS[0]], got[LC.POISONS[1]]
             LC.check_same(la, ga, lb, gb, wants, tag="zstd")
+
+
+# ---- the edge cases, the capacity sweep, persistent waves, the mutations ---------------------------------------------------------------
+def _edge():
+    return [dict(name=c["name"], blob=c["blob"], dict=c["dict"]) for c in Z.golden_more() + Z.edge_cases()]
+
+
+def test_edge_cases_from_host_memory_from_device_memory_and_again(ctx):
+    cases = _edge()
+    caps = [_slot(c) for c in cases]
+    host = call(ctx, cases, caps)
+    check(cases, host, caps)
+    by_name = {c["name"]: (int(host["status"][i]), int(host["out_len"][i])) for i, c in enumerate(cases)}
+    assert {c["name"]: by_name[c["name"]] for c in Z.edge_cases()} == \
+           {c["name"]: (R.STATUS[c["status"]], c["size"] or 0) for c in Z.edge_cases()}
+    dev = call(ctx, cases, caps, device=True)
+    check(cases, dev, caps)
+    assert same(dev, host)
+    again = call(ctx, cases, caps)
+    check(cases, again, caps)
+    assert same(again, host)
+
+
+def test_capacity_sweep_in_one_call(ctx):
+    """slots that end inside a literal run, a match, a batch of 64 sequences or between frames: the status, the exact size, the bytes
+    consumed, and nothing stored at or beyond the capacity; nothing is asserted about the bytes inside a slot too small"""
+    cases = Z.capacity_sweep()
+    assert len(set(c["blob"] for c in cases)) >= 40 and len(cases) >= 200
+    caps = [c["cap"] for c in cases]
+    r = call(ctx, cases, caps)
+    for i, c in enumerate(cases):
+        st, data, out_len, used = R.outcome(c["blob"], c["dict"] or b"", c["cap"])
+        got = (int(r["status"][i]), int(r["out_len"][i]), int(r["in_used"][i]))
+        assert got == (R.STATUS[st], out_len, used), (c["name"], got, st, out_len, used)
+    assert S.untouched_outside(r["out"], r["out_off"], r["out_cap"])
+    by_name = {c["name"]: int(r["status"][i]) for i, c in enumerate(cases)}
+    assert by_name["bad_sum_then_overflow@22"] == R.STATUS["E_ZSTD_CHECKSUM"] and by_name["bad_sum_then_overflow@21"] == TOO_SMALL
+
+
+def test_persistent_waves_keep_nothing_of_the_file_before(ctx):
+    """4160 files on the call's 2048 waves: every wave decodes two files and 64 decode three with one literal buffer, one set of tables
+    and one set of counters (zstd_cases.persistent_files)"""
+    cases = Z.persistent_files()
+    assert len(cases) == 2 * 2048 + 64
+    want = [Z.expected(c["blob"], c["dict"]) for c in cases]
+    caps = [w[2] if w[0] == "OK" else 64 for w in want]
+    assert {"OK", "E_EOF", "E_ZSTD_DATA"} == set(w[0] for w in want)
+    for k, name in ((2048 + 0, "treeless_without_table"), (2048 + 1, "repeat_mode_without_table"), (2048 + 6, "offset_beyond_history"),
+                    (2048 + 4, "treeless_with_the_table_of_the_file_before"), (2048 + 5, "repeat_mode_with_the_tables_of_the_file_before"),
+                    (4096 + 2, "treeless_with_the_table_of_the_file_before"), (4096 + 3, "repeat_mode_with_the_tables_of_the_file_before")):
+        assert cases[k]["name"] == name and want[k][0] == "E_ZSTD_DATA"
+    for device in (False, True):
+        r = call(ctx, cases, caps, device)
+        got = [(int(r["status"][i]), int(r["out_len"][i]), int(r["in_used"][i])) for i in range(len(cases))]
+        exp = [(R.STATUS[w[0]], w[2], w[3]) for w in want]
+        wrong = [(i, cases[i]["name"], got[i], exp[i]) for i in range(len(cases)) if got[i] != exp[i]]
+        assert not wrong, (len(wrong), wrong[:8])
+        wrong = [(i, cases[i]["name"]) for i in range(len(cases)) if want[i][0] == "OK" and r["data"][i] != want[i][1]]
+        assert not wrong, (len(wrong), wrong[:8])
+        assert S.untouched_outside(r["out"], r["out_off"], r["out_cap"])
+
+
+def test_mutations_in_one_call(ctx):
+    cases = [dict(name=m["name"], blob=m["blob"], dict=None) for m in Z.mutations()]
+    assert len(cases) >= 596
+    caps = [max(Z.expected(c["blob"])[2], 16) for c in cases]
+    check(cases, call(ctx, cases, caps), caps)
+
+
+def test_decode_many_over_the_edge_cases(ctx):
+    """the Python layer: the frames that declare no size go through the size query and the retry"""
+    cases = _edge()
+    assert sum(1 for c in cases if zstd.declared_size(c["blob"]) is None and Z.expected(c["blob"], c["dict"])[0] == "OK") >= 16
+    res = zstd.decode_many([c["blob"] for c in cases], dictionary=[c["dict"] for c in cases], ctx=ctx, return_exceptions=True)
+    kinds = {"E_ZSTD_DATA": zstd.DataError, "E_ZSTD_CHECKSUM": zstd.ChecksumError}
+    for c, r in zip(cases, res):
+        st, data = Z.expected(c["blob"], c["dict"])[:2]
+        if st == "OK":
+            assert r == data, c["name"]
+        else:
+            assert type(r) is kinds[st] and r.status == R.STATUS[st], (c["name"], r)
+    with pytest.raises(zstd.FilesFailed):
+        zstd.decode_many([c["blob"] for c in cases], dictionary=[c["dict"] for c in cases], ctx=ctx)

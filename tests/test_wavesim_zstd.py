@@ -1,7 +1,8 @@
 """The Zstandard decoder (rust_compress_amd/csrc/k_zstd.hip with k_xxh64.hip, UNMODIFIED) and the host's rcx_plan_zstd on the wave64
 simulator, against tests/zstd_ref.py: every named and crafted input in one call with slots of exactly the decoded size, the statuses by
-name, the size query and the exact retry, the dictionary cases, the 200 single-bit flips, guard bytes around every slot.  Every
-malformed input runs to completion.  CPU only."""
+name, the size query and the exact retry, the dictionary cases, the 200 single-bit flips, guard bytes around every slot; the edge cases (zstd_cases.edge_cases(), golden_more())
+in both executors and on two waves, persistent waves over files that would show what the file before left, the capacity sweep, the 600
+mutations.  Every malformed input runs to completion.  CPU only."""
 import numpy as np
 import pytest
 
@@ -130,3 +131,85 @@ def test_the_plan_refuses_what_the_header_says():
     st = np.zeros(4, np.int32)
     rc = lib.sim_zstd_decode(p(z), p(z), p(z), p(z), None, p(z), p(z), p(z), p(z), p(z), p(st), 1, 0, p(z), err, 256)
     assert rc == -1 and b"together" in err.value
+
+
+# ---- the edge cases, the capacity sweep, the mutations ----------------------------------------------------------------------------------
+def _edge():
+    return [dict(name=c["name"], blob=c["blob"], dict=c["dict"]) for c in Z.golden_more() + Z.edge_cases()]
+
+
+def _exact(cases):
+    return [Z.expected(c["blob"], c["dict"])[2] if Z.expected(c["blob"], c["dict"])[0] == "OK" else 64 for c in cases]
+
+
+@pytest.fixture(scope="module")
+def edges():
+    cases = _edge()
+    caps = _exact(cases)
+    return cases, caps, S.run([c["blob"] for c in cases], caps, [c["dict"] for c in cases])
+
+
+def test_edge_cases_in_exact_slots(edges):
+    cases, caps, r = edges
+    assert r["waves"] == len(cases)
+    check(cases, r, caps)
+    by_name = {c["name"]: int(r["status"][i]) for i, c in enumerate(cases)}
+    assert {c["name"]: by_name[c["name"]] for c in Z.edge_cases()} == {c["name"]: R.STATUS[c["status"]] for c in Z.edge_cases()}
+    assert {c["name"]: int(r["out_len"][i]) for i, c in enumerate(cases) if by_name[c["name"]] == 0} == \
+           dict([(c["name"], c["size"]) for c in Z.edge_cases() if c["status"] == "OK"] + [(g["name"], len(g["raw"])) for g in Z.golden_more()])
+
+
+def test_edge_cases_in_the_executor_built_first_and_on_two_waves(edges):
+    cases, caps, r = edges
+    blobs, dicts = [c["blob"] for c in cases], [c["dict"] for c in cases]
+    plain = S.run(blobs, caps, dicts, variant=2)
+    check(cases, plain, caps)
+    assert plain["data"] == r["data"]
+    two = S.run(blobs, caps, dicts, waves=2)
+    assert two["waves"] == 2
+    check(cases, two, caps)
+    assert two["data"] == r["data"]
+
+
+def test_persistent_waves_keep_nothing_of_the_file_before():
+    """tests/test_gpu_zstd.py's files on 12 waves: each takes two of a triple, six take all three"""
+    cases = Z.persistent_files(n=30, waves=12)
+    caps = _exact(cases)
+    for variant in (0, 2):
+        r = S.run([c["blob"] for c in cases], caps, [c["dict"] for c in cases], waves=12, variant=variant)
+        assert r["waves"] == 12
+        check(cases, r, caps)
+    refused = {c["name"]: int(r["status"][i]) for i, c in enumerate(cases) if i >= 12 and int(r["status"][i])}
+    assert refused == {name: R.STATUS["E_ZSTD_DATA"] for name in (
+        "treeless_without_table", "repeat_mode_without_table", "offset_beyond_history", "treeless_with_the_table_of_the_file_before",
+        "repeat_mode_with_the_tables_of_the_file_before", "treeless_in_second_frame_alone")}
+    assert cases[4]["name"] == "bits3_4000_l1" and cases[16]["name"] == "treeless_with_the_table_of_the_file_before"   # one wave's, in turn
+    assert cases[15]["name"] == cases[5]["name"] == "rle_tables" and cases[27]["name"] == cases[17]["name"] == "repeat_mode_with_the_tables_of_the_file_before"
+
+
+@pytest.mark.parametrize("variant", [0, 2])
+def test_capacity_sweep(variant):
+    """nothing at or beyond a capacity that ends inside a literal run, a match, a batch or between frames; the size is still exact"""
+    cases = Z.capacity_sweep()
+    assert len(set(c["blob"] for c in cases)) >= 40 and len(cases) >= 200
+    caps = [c["cap"] for c in cases]
+    r = S.run([c["blob"] for c in cases], caps, [c["dict"] for c in cases], variant=variant)
+    assert r["rc"] == 0, r["err"]
+    small = 0
+    for i, c in enumerate(cases):
+        st, data, out_len, used = R.outcome(c["blob"], c["dict"] or b"", c["cap"])
+        got = (int(r["status"][i]), int(r["out_len"][i]), int(r["in_used"][i]))
+        assert got == (R.STATUS[st], out_len, used), (c["name"], got, st, out_len, used)
+        small += st == "E_OUTPUT_TOO_SMALL"
+    assert S.untouched_outside(r["out"], r["out_off"], r["out_cap"])
+    by_name = {c["name"]: int(r["status"][i]) for i, c in enumerate(cases)}
+    assert by_name["bad_sum_then_overflow@22"] == R.STATUS["E_ZSTD_CHECKSUM"] and by_name["bad_sum_then_overflow@21"] == R.STATUS["E_OUTPUT_TOO_SMALL"]
+    assert small >= len(cases) - 8                                   # (all but the files that decode to 0 or 1 bytes, and the checksum)
+
+
+def test_mutations():
+    mu = Z.mutations()
+    assert len(mu) >= 596
+    caps = [max(Z.expected(m["blob"])[2], 16) for m in mu]
+    r = S.run([m["blob"] for m in mu], caps)
+    check([dict(name=m["name"], blob=m["blob"], dict=None) for m in mu], r, caps)

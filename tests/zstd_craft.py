@@ -92,15 +92,16 @@ LL_BITS = [0] * 16 + [1, 1, 1, 1, 2, 2, 3, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14,
 ML_BITS = [0] * 32 + [1, 1, 1, 1, 2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16]
 
 
-def rle_sequences(ll_code, of_code, ml_code, extras, left_over=0):
+def rle_sequences(ll_code, of_code, ml_code, extras, left_over=0, repeat=False):
     """the sequences section with all three tables in RLE mode: extras is one (offset bits, match length bits, literal length bits) per
-    sequence; left_over: that many zero bits nobody reads"""
+    sequence; left_over: that many zero bits nobody reads; repeat: the three tables in repeat mode instead, for a block behind one
+    that set these codes"""
     fields = []
     for ov, mv, lv in extras:
         fields += [(ov, of_code), (mv, ML_BITS[ml_code]), (lv, LL_BITS[ll_code])]
     if left_over:
         fields.append((0, left_over))
-    return nseq_bytes(len(extras)) + bytes([0x54, ll_code, of_code, ml_code]) + backward(fields)
+    return nseq_bytes(len(extras)) + (b"\xfc" if repeat else bytes([0x54, ll_code, of_code, ml_code])) + backward(fields)
 
 
 def compressed(lits, seqs=b"\x00", last=False):

@@ -5,7 +5,13 @@ this decoder and the kernel are stricter than libzstd.
 
 decode(blob, dictionary=b"", cap=None) -> (bytes, in_used) for one whole file (concatenated frames, skippable frames skipped, trailing
 bytes that are no magic left alone), or raises ZstdRefError with .status, the name of the rcx status.  Slow and simple on purpose: a
-bitstream is one Python integer.  Also xxh64()."""
+bitstream is one Python integer.  Also xxh64().
+
+decode(trace=[]) appends what the file reaches: ("frame", ...), ("block", type, size), ("lit", ...), ("nseq", ...), ("modes", ...) and
+one-word entries for the paths the kernel has a branch for -- lithdr{1,2,3}_{raw,rle}, hufhdr{3,4,5}, lit_full, rep{1,2,3} and
+rep{1,2,3}_ll0 (offset_value 1, 2, 3 behind literals and behind none; rep3_ll0 is rep0 - 1), zero_as_1, ll_bits>=8, ml_bits>=14,
+of_code>=20, far, overlap, dict, dict_straddle, frame2_compressed, weights_end_state{1,2}.  tests/zstd_cases.props turns a trace into a
+set of words."""
 
 MAGIC = 0xFD2FB528
 BLOCK_MAX = 128 * 1024
@@ -191,8 +197,10 @@ LIMITS = {"ll": (35, 9), "of": (31, 8), "ml": (52, 9)}
 HUF_LOG = 11
 
 
-def read_huffman(data):
-    """the table description at the head of `data` -> (table of (symbol, length) indexed by the next `log` bits, log, bytes consumed)"""
+def read_huffman(data, trace=None):
+    """the table description at the head of `data` -> (table of (symbol, length) indexed by the next `log` bits, log, bytes consumed);
+    trace: gets which of the two interleaved states ran off an FSE weight stream"""
+    trace = [] if trace is None else trace
     if not data:
         raise _data("no huffman description")
     hb = data[0]
@@ -223,6 +231,7 @@ def read_huffman(data):
             s1 = base + b.read(nb)
             if b.over:
                 w.append(tab[s2][0])
+                trace.append(("weights_end_state1",))
                 break
             if len(w) > 253:
                 raise _data("more than 255 weights")
@@ -231,6 +240,7 @@ def read_huffman(data):
             s2 = base + b.read(nb)
             if b.over:
                 w.append(tab[s1][0])
+                trace.append(("weights_end_state2",))
                 break
     if any(x > HUF_LOG for x in w):
         raise _data("huffman weight over 11")
@@ -273,8 +283,9 @@ def huffman_stream(data, table, log, count):
 
 # ---- frames --------------------------------------------------------------------------------------------------------------------------
 class _Frame:
-    def __init__(self, dictionary, trace=None):
+    def __init__(self, dictionary, trace=None, index=0):
         self.dict = dictionary
+        self.index = index                                       # which of the file's Zstandard frames this is
         self.trace = trace if trace is not None else []
         self.out = bytearray()
         self.huf = None
@@ -294,6 +305,7 @@ class _Frame:
             if hs > len(blk) or size > BLOCK_MAX:
                 raise _data("literals header")
             self.trace.append(("lit", ("raw", "rle")[kind], 0, ""))
+            self.trace.append(("lithdr%d_%s" % (hs, ("raw", "rle")[kind]),))
             if kind == 0:
                 if hs + size > len(blk):
                     raise _data("raw literals run past the block")
@@ -315,9 +327,12 @@ class _Frame:
         if size > BLOCK_MAX or hs + csize > len(blk) or not size:
             raise _data("compressed literals header")
         body = blk[hs:hs + csize]
+        self.trace.append(("hufhdr%d" % hs,))
+        if size == BLOCK_MAX:
+            self.trace.append(("lit_full",))                    # the literals fill the kernel's buffer
         self.trace.append(("lit", ("huffman", "treeless")[kind - 2], streams, ("direct" if body and body[0] >= 128 else "fse") if kind == 2 else ""))
         if kind == 2:
-            table, log, used = read_huffman(body)
+            table, log, used = read_huffman(body, self.trace)
             self.huf = (table, log)
             body = body[used:]
         elif self.huf is None:
@@ -352,6 +367,8 @@ class _Frame:
     def block(self, blk):
         if len(blk) < 3 or len(blk) >= BLOCK_MAX:
             raise _data("compressed block of %d bytes" % len(blk))
+        if self.index:
+            self.trace.append(("frame2_compressed",))
         lits, used = self.literals(blk)
         rest = blk[used:]
         if not rest:
@@ -398,6 +415,14 @@ class _Frame:
             ov = b.read(oc)
             mlen = ML_CODE[c_ml][0] + b.read(ML_CODE[c_ml][1])
             llen = LL_CODE[c_ll][0] + b.read(LL_CODE[c_ll][1])
+            if LL_CODE[c_ll][1] >= 8:
+                self.trace.append(("ll_bits>=8",))
+            if ML_CODE[c_ml][1] >= 14:
+                self.trace.append(("ml_bits>=14",))
+            if oc >= 20:
+                self.trace.append(("of_code>=20",))
+            if oc <= 1:                                          # offset_value 1, 2, 3: the repeat offsets
+                self.trace.append(("rep%d%s" % (1 + oc + ov, "" if llen else "_ll0"),))
             if oc > 1:
                 off = (1 << oc) + ov - 3
                 rep[:] = [off, rep[0], rep[1]]
@@ -410,7 +435,9 @@ class _Frame:
             else:
                 idx = 1 + (0 if llen else 1) + ov
                 off = rep[0] - 1 if idx == 3 else rep[idx]
-                off = off or 1                                   # (libzstd reads a zero as 1)
+                if not off:
+                    self.trace.append(("zero_as_1",))
+                    off = 1                                      # (libzstd reads a zero as 1)
                 rep[:] = [off, rep[0], rep[1]] if idx != 1 else [off, rep[0], rep[2]]
             if llen > len(lits) - lp:
                 raise _data("literal length past the literals")
@@ -426,6 +453,8 @@ class _Frame:
                 self.trace.append(("dict",))
                 d = off - len(out)
                 take = min(d, mlen)
+                if take < mlen:
+                    self.trace.append(("dict_straddle",))       # ... and ends in the frame's output
                 out += self.dict[len(self.dict) - d:len(self.dict) - d + take]
                 mlen -= take
             if mlen:
@@ -449,7 +478,7 @@ def decode(blob, dictionary=b"", cap=None, trace=None):
     """-> (bytes, in_used).  cap: the slot's capacity; a result longer than it raises E_OUTPUT_TOO_SMALL with .size, after every other
     check but the content checksums of frames that end beyond it."""
     blob, dictionary = bytes(blob), bytes(dictionary or b"")
-    pos, frames, total = 0, 0, bytearray()
+    pos, frames, zframes, total = 0, 0, 0, bytearray()
     while True:
         if len(blob) - pos < 4:
             if frames:
@@ -490,7 +519,8 @@ def decode(blob, dictionary=b"", cap=None, trace=None):
         q += dids
         fcs = int.from_bytes(blob[q:q + fcss], "little") + (256 if fcss == 2 else 0)
         pos += hsize
-        f = _Frame(dictionary, trace)
+        f = _Frame(dictionary, trace, zframes)
+        zframes += 1
         f.trace.append(("frame", fcss, 0 if single else 1, (fhd >> 2) & 1))
         while True:
             if len(blob) - pos < 3:
