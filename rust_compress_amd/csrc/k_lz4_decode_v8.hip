@@ -12,8 +12,9 @@
 // the token starts it visits inside its segment in a 64-bit register; the lane that holds the true cursor starts there.  Then
 // the segments are LINKED in order (scalar code over registers, no memory): the true walk enters segment k where the last
 // true segment's walk left; if that byte is marked in k's map the two walks have met, the marks below it are dropped and k's
-// exit is the true one; if not (a few per cent) the true walk is followed by hand until it meets the map or leaves the
-// segment.  A segment the true walk jumps over (a long literal run) is cleared.  What is left is the exact set of token
+// exit is the true one; if not (13 segments of a 64 KiB block of text) the segment is decoded once more, a lane per BYTE, into
+// a table of hop distances, and the true walk runs over that table at three scalar instructions a token (rcx_hop_walk): its marks
+// are the segment's map, where it leaves the segment is the exit.  A segment the true walk jumps over (a long literal run) is cleared.  What is left is the exact set of token
 // starts, and from there on everything is a lane per TOKEN: the maps are unpacked into a list of positions, 64 list entries
 // make a batch, and each lane reads its token's fields from 16 bytes of the staged input (token, <= 12 literals, offset and
 // the first length extension fit; the few others, and the last 20 bytes of a block, take a bounds-checked byte path through
@@ -46,7 +47,13 @@
                                             nothing else runs on the SIMD (3: 0.5224; 4 with LOW 2 / 3 / 4 / 6: 0.5233 / 0.5220 / 0.5229 / 0.5240 -- no better than 3) */
 #endif
 #ifndef RCX_V8_PRE
-#define RCX_V8_PRE 128                     /* the guessing lanes' head start, bytes (the kernel template's default) */
+#define RCX_V8_PRE 128                     /* the guessing lanes' head start, bytes (the kernel template's default; a multiple of 16).  With the hop-table repair
+                                            (RCX_LINK_REPAIR): 32 / 48 / 64 / 80 / 96 / 128 = 0.469 / 0.443 / 0.433 / 0.4260 / 0.4268 / 0.4284 ms against 0.4369 without it --
+                                            80 and 96 are within the runs' spread of 128 and no faster in the kernel trace, so 128 stays */
+#endif
+#ifndef RCX_LINK_REPAIR
+#define RCX_LINK_REPAIR 1                  /* a failed link is repaired over a pre-decoded hop table of the segment (rcx_hop_walk); 0: token by token with next_tok_c until
+                                            the walk meets the lane's map (A/B): 0.4369 -> 0.4284 ms, 412 -> 375 scalar and 549.5 -> 547 vector instructions a batch */
 #endif
 #ifndef RCX_WALK_STEPS
 #define RCX_WALK_STEPS 16                  /* steps of the ISA walk between two looks at the ring (ring_prio): 4 / 8 / 16 / 64: 0.4604 / 0.4587 / 0.4565 / 0.479 ms */
@@ -1094,11 +1101,43 @@ struct Lz4V8 : Lz4X6<Lz4V5<1024, TC, HH, PROF8, SB, false, MIRROR>, PROF8> {
                             if (PROF8) pp[8] += 1;
                             uint64_t tm = 0;
                             uint32_t q = cin;
+#if RCX_LINK_REPAIR
+                            // The segment pre-decoded once, a lane per byte (Lz4V4::collect's register window): the hop of a token that
+                            // would start there, or 128 where next_tok_c would not decide it from the staged bytes alone (a literal length
+                            // of 15 or more, a match-length extension that goes on, the block's last 20 bytes).  The chain from `cin` is
+                            // then 3 scalar instructions a hop, its marks ARE the segment's map (the lane's own guess is not consulted),
+                            // and where it leaves the 64 bytes is the true exit.  A general token is stepped over by next_tok_c, as in
+                            // the loop this replaces, and the chain goes on over the table behind it.
+                            {
+                                const int32_t qi = (int32_t)(sk + lane) - this->cbase;         // PRE + 64 k + lane: staged, and so are the 17 bytes behind it
+                                const uint32_t t = ((const RCX_LDS_AS uint8_t*)this->cbuf)[qi];
+                                const uint32_t L = t >> 4;
+                                const uint32_t x = ((const RCX_LDS_AS uint8_t*)this->cbuf)[qi + 3 + (int32_t)L];
+                                const bool ext = (t & 15u) == 15u;
+                                const bool fastp = n >= 20u && sk + lane <= n - 20u && L != 15u && !(ext && x == 255u);
+                                const uint32_t dv = fastp ? (ext ? 4u : 3u) + L : 128u;
+                                uint32_t rel = cin - sk;
+                                RCX_V8_STAT(7, lane == 0);                                     // (simulator: failed links)
+                                for (;;) {
+                                    uint64_t vis = 0;
+                                    RCX_HOP_WALK(dv, rel, vis);
+                                    tm |= vis;
+                                    RCX_V8_STAT(7, lane == 0 ? (uint64_t)__popcll(vis) << 32 : 0ull); RCX_V8_STAT(19, lane == 0 && rel >= 128u);   // (... | hops << 32, general tokens)
+                                    if (rel < 128u) { q = sk + rel; break; }                   // the exit: >= sk + 64 >= ek
+                                    q = RCX_U(next_tok_c(sk + rel - 128u));
+                                    if (q >= ek) break;
+                                    rel = q - sk;
+                                }
+                            }
+                            if ((int)lane == k) { map = tm; lowv = 0; clr = false; }
+                            X = q;
+#else
                             while (q < ek && !((mk >> (q - sk)) & 1ull)) { tm |= 1ull << (q - sk); q = RCX_U(next_tok_c(q)); }
                             const bool merged = q < ek;
                             const uint64_t nm = (merged ? mk & ~((1ull << (q - sk)) - 1ull) : 0ull) | tm;
                             if ((int)lane == k) { map = nm; lowv = 0; clr = false; }
                             X = merged ? exk : q;
+#endif
                         }
                     }
                     if (k == nseg - 1) c = X;
