@@ -27,6 +27,23 @@ def _adler32(d):
     return zlib.adler32(d) if d else 0
 
 
+def _ptr(a):
+    """an optional array -> its address, or None: a null pointer"""
+    return a.ctypes.data if a is not None else None
+
+
+def _u64(a):
+    """one of a batch's per-block arrays as the library reads it: contiguous uint64 (one zero where there is no block: memory behind the pointer)"""
+    a = np.ascontiguousarray(a, np.uint64)
+    return a if a.size else np.zeros(1, np.uint64)
+
+
+def _slots(caps):
+    """output capacities -> Context._batch's `out`: a zeroed buffer of 16-byte aligned slots, their offsets, the capacities"""
+    total, off, cap = B.layout(caps)
+    return np.zeros(total, dtype=np.uint8), off, cap
+
+
 def _pack_hist(blobs, histories, limit):
     """the input buffer history, block, history, block, ...: -> (uint8 array, in_off, hist_len); a history's last `limit` bytes count"""
     buf, off, hl = bytearray(), [], []
@@ -120,33 +137,46 @@ class Context:
         self._chk(N.lib().rcx_ctx_set_stream(self._h, C.c_void_p(stream_ptr)))
 
     # ---------------- host-memory batches ----------------
-    def _run_host(self, fn_name, blobs, caps, extra_in=None, extra_out=False, n_out=None, needs_out=True, scalar=None):
-        n = len(blobs)
-        base, off, lens = B.pack(blobs)
-        total, ooff, ocap = B.layout(caps if needs_out else [0] * n)
-        out = np.zeros(total, dtype=np.uint8)
+    def _batch(self, fn_name, base, in_off, in_len, out, *extra, unpack=True):
+        """THE host-memory call: builds the rcx_batch, calls fn_name, unpacks -> Result (aux None).  base: a numpy uint8 array; out: (buffer,
+        out_off, out_cap), or None for the entry points without slots (the hashes: four null pointers).  extra: what follows the batch in
+        include/rcx.h -- a numpy array goes as its address (the caller has made it contiguous and of the element type), None as a null
+        pointer, anything else as it is.  unpack=False: outputs None, for the caller that reads the buffer itself (a chain of linked LZ4
+        blocks shares its head's slot)."""
+        n = len(in_off)
+        in_off, in_len = _u64(in_off), _u64(in_len)
+        if base.size == 0:
+            base = np.zeros(1, np.uint8)
+        buf, out_off, out_cap = (out[0], _u64(out[1]), _u64(out[2])) if out is not None else (None, None, None)
         out_len = np.zeros(max(n, 1), np.uint64)
         in_used = np.zeros(max(n, 1), np.uint64)
         status = np.zeros(max(n, 1), np.int32)
-        p = lambda a: a.ctypes.data
-        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
-        fn = getattr(N.lib(), fn_name)
-        aux = None
+        b = N.Batch(_ptr(base), _ptr(in_off), _ptr(in_len), _ptr(buf), _ptr(out_off), _ptr(out_cap), _ptr(out_len) if out is not None else None,
+                    _ptr(in_used), _ptr(status), n, N.MEM_HOST)
+        args = [C.c_void_p(_ptr(a)) if a is None or isinstance(a, np.ndarray) else a for a in extra]
+        self._chk(getattr(N.lib(), fn_name)(self._h, C.byref(b), *args))
+        outs = None if not unpack else B.unpack(buf, out_off, out_len[:n]) if out is not None else [b""] * n
+        return Result(outs, out_len[:n], in_used[:n], status[:n], None)
+
+    def _run_host(self, fn_name, blobs, caps, extra_in=None, extra_out=False, n_out=None, needs_out=True, scalar=None):
+        n = len(blobs)
+        base, off, lens = B.pack(blobs)
+        aux, extra = None, ()
         if scalar is not None:
-            self._chk(fn(self._h, C.byref(b), scalar))
+            extra = (scalar,)
         elif extra_in is not None:
             aux = np.ascontiguousarray(extra_in, dtype=np.uint32)
-            self._chk(fn(self._h, C.byref(b), C.c_void_p(p(aux))))
+            extra = (aux,)
         elif n_out is not None:
-            no = np.ascontiguousarray(n_out, dtype=np.uint64)
-            self._chk(fn(self._h, C.byref(b), C.c_void_p(p(no))))
+            extra = (np.ascontiguousarray(n_out, dtype=np.uint64),)
         elif extra_out:
             aux = np.zeros(max(n, 1), np.uint32)
-            self._chk(fn(self._h, C.byref(b), C.c_void_p(p(aux))))
-        else:
-            self._chk(fn(self._h, C.byref(b)))
-        outs = B.unpack(out, ooff, out_len[:n]) if needs_out else [b""] * n
-        return Result(outs, out_len[:n], in_used[:n], status[:n], aux[:n] if aux is not None else None)
+            extra = (aux,)
+        res = self._batch(fn_name, base, off, lens, _slots(caps if needs_out else [0] * n), *extra)     # (no output: slots of capacity 0)
+        if not needs_out:
+            res.outputs = [b""] * n
+        res.aux = aux[:n] if aux is not None else None
+        return res
 
     def lz4_decode_blocks(self, blobs, caps):
         return self._run_host("rcx_lz4_decode_batch", blobs, caps)
@@ -165,25 +195,19 @@ class Context:
         """rcx_lz4_encode_hc_hist_batch over a buffer the caller laid out: block i is base[in_off[i] : in_off[i] + in_len[i]] (base: a
         numpy uint8 array) and its matches may reach into the hist_len[i] bytes below in_off[i] -- a dictionary put there, or the
         block before it (linked blocks).  hist_len None: no history."""
-        n = len(in_off)
-        off = np.ascontiguousarray(in_off, np.uint64)
-        lens = np.ascontiguousarray(in_len, np.uint64)
         if caps is None:
-            caps = [max(int(N.lib().rcx_lz4_compression_bound(int(l))), 1) for l in lens]
-        total, ooff, ocap = B.layout(caps)
-        out = np.zeros(total, dtype=np.uint8)
-        out_len = np.zeros(max(n, 1), np.uint64)
-        in_used = np.zeros(max(n, 1), np.uint64)
-        status = np.zeros(max(n, 1), np.int32)
+            caps = [max(int(N.lib().rcx_lz4_compression_bound(int(l))), 1) for l in in_len]
+        return self._encode_hist("rcx_lz4_encode_hc_hist_batch", base, in_off, in_len, hist_len, level, caps)
+
+    def _encode_hist(self, fn_name, base, in_off, in_len, hist_len, level, caps, dict_id=None):
+        """one rcx_*_encode_hist_batch call (dict_id: rcx_zlib_encode_dict_batch) over a buffer the caller laid out (base: a numpy uint8 array)"""
+        n = len(in_off)
+        out = _slots(caps)
         hist = np.ascontiguousarray(hist_len, np.uint64) if hist_len is not None else None
         if hist is not None and hist.size != n:
             raise ValueError("hist_len: one entry per block")
-        if base.size == 0:
-            base = np.zeros(1, np.uint8)
-        p = lambda a: a.ctypes.data
-        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
-        self._chk(N.lib().rcx_lz4_encode_hc_hist_batch(self._h, C.byref(b), int(level), C.c_void_p(p(hist) if hist is not None and n else None)))
-        return Result(B.unpack(out, ooff, out_len[:n]), out_len[:n], in_used[:n], status[:n], None)
+        ids = (np.array(list(dict_id) or [0], np.uint32),) if dict_id is not None else ()
+        return self._batch(fn_name, base, in_off, in_len, out, int(level), hist if n else None, *ids)     # (no block: a null pointer)
 
     def lz4_encode_hc_hist_blocks(self, blobs, histories, level=9, caps=None):
         """One LZ4 block per blob from the high-compression encoder, with HISTORY: histories[i] (bytes or None; its last 64 KiB count)
@@ -191,44 +215,31 @@ class Context:
         the same bytes (rcx_lz4_decode_linked_batch with dict_len, or any LZ4 decoder given them as its dictionary)."""
         if len(histories) != len(blobs):
             raise ValueError("histories: one entry (bytes or None) per blob")
-        buf, off, hl = bytearray(), [], []
-        for blob, h in zip(blobs, histories):
-            h = bytes(h)[-65536:] if h else b""
-            buf += h
-            off.append(len(buf))
-            hl.append(len(h))
-            buf += bytes(blob)
-        base = np.frombuffer(bytes(buf) + b"\0" * 16, np.uint8)
+        base, off, hl = _pack_hist(blobs, histories, 65536)
         return self.lz4_encode_hc_hist(base, off, [len(b) for b in blobs], hl, level, caps)
 
-    def _shared(self, fn_name, base, in_off, in_len, dict_off, dict_len, level, caps, dict_id=None):
-        """one rcx_*_encode_shared_batch call over a buffer the caller laid out (base: a numpy uint8 array)"""
+    def _shared(self, fn_name, base, in_off, in_len, dict_off, dict_len, caps, level=None, flags=False, dict_id=None):
+        """one rcx_*_shared_batch call over a buffer the caller laid out (base: a numpy uint8 array): an encode (level) or a decode (flags: the
+        entry point fills a flags array, the result's aux).  Nothing lies in front of a slot."""
         n = len(in_off)
-        off = np.ascontiguousarray(in_off, np.uint64) if n else np.zeros(1, np.uint64)
-        lens = np.ascontiguousarray(in_len, np.uint64) if n else np.zeros(1, np.uint64)
-        total, ooff, ocap = B.layout(caps)
-        out = np.zeros(total, dtype=np.uint8)
-        out_len = np.zeros(max(n, 1), np.uint64)
-        in_used = np.zeros(max(n, 1), np.uint64)
-        status = np.zeros(max(n, 1), np.int32)
+        out = _slots(caps)
         if (dict_off is None) != (dict_len is None):
             raise ValueError("dict_off and dict_len: both or neither")
         d_off = d_len = None
         if dict_len is not None:
-            d_off = np.ascontiguousarray(dict_off, np.uint64) if n else np.zeros(1, np.uint64)
-            d_len = np.ascontiguousarray(dict_len, np.uint64) if n else np.zeros(1, np.uint64)
+            d_off, d_len = _u64(dict_off), _u64(dict_len)
             if n and (d_off.size != n or d_len.size != n):
                 raise ValueError("dict_off, dict_len: one entry per block")
-        if base.size == 0:
-            base = np.zeros(1, np.uint8)
-        p = lambda a: a.ctypes.data
-        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
-        args = [self._h, C.byref(b), int(level), C.c_void_p(p(d_off) if d_off is not None else None), C.c_void_p(p(d_len) if d_len is not None else None)]
+        extra = [int(level)] if level is not None else []
+        aux = np.zeros(max(n, 1), np.uint32) if flags else None
+        if flags:
+            extra.append(aux)
+        extra += [d_off, d_len]
         if dict_id is not None:
-            ids = np.array(list(dict_id) or [0], np.uint32)
-            args.append(C.c_void_p(p(ids)))
-        self._chk(getattr(N.lib(), fn_name)(*args))
-        return Result(B.unpack(out, ooff, out_len[:n]), out_len[:n], in_used[:n], status[:n], None)
+            extra.append(np.array(list(dict_id) or [0], np.uint32))
+        res = self._batch(fn_name, base, in_off, in_len, out, *extra)
+        res.aux = aux[:n] if flags else None
+        return res
 
     def lz4_encode_hc_shared(self, base, in_off, in_len, dict_off, dict_len, level=9, caps=None):
         """rcx_lz4_encode_hc_shared_batch over a buffer the caller laid out: block i is base[in_off[i] : in_off[i] + in_len[i]] (base: a
@@ -237,7 +248,7 @@ class Context:
         same block with the same dictionary directly in front of it.  dict_off and dict_len None: lz4_encode_hc_blocks' results."""
         if caps is None:
             caps = [max(int(N.lib().rcx_lz4_compression_bound(int(l))), 1) for l in in_len]
-        return self._shared("rcx_lz4_encode_hc_shared_batch", base, in_off, in_len, dict_off, dict_len, level, caps)
+        return self._shared("rcx_lz4_encode_hc_shared_batch", base, in_off, in_len, dict_off, dict_len, caps, level)
 
     def lz4_encode_hc_dict_blocks(self, blobs, dictionary, level=9, caps=None):
         """One LZ4 HC block per blob behind a dictionary (bytes for all blobs, or a list with one entry, bytes or None, per blob; the last
@@ -252,7 +263,7 @@ class Context:
         directly in front of it."""
         if caps is None:
             caps = [deflate_bound(int(l)) for l in in_len]
-        return self._shared("rcx_deflate_encode_shared_batch", base, in_off, in_len, dict_off, dict_len, level, caps)
+        return self._shared("rcx_deflate_encode_shared_batch", base, in_off, in_len, dict_off, dict_len, caps, level)
 
     def deflate_encode_dict_blocks(self, blobs, dictionary, level=6, caps=None):
         """One raw DEFLATE stream per blob (levels 2..9) behind a dictionary (bytes for all blobs, or a list with one entry, bytes or
@@ -261,46 +272,12 @@ class Context:
         base, off, lens, d_off, d_len, _ = _pack_shared(blobs, dictionary, 32768)
         return self.deflate_encode_shared(base, off, lens, d_off, d_len, level, caps)
 
-    def _shared_decode(self, fn_name, base, in_off, in_len, dict_off, dict_len, caps, flags=False, dict_id=None):
-        """one rcx_*_shared_batch decode over a buffer the caller laid out (base: a numpy uint8 array).  Nothing lies in front of a slot."""
-        n = len(in_off)
-        off = np.ascontiguousarray(in_off, np.uint64) if n else np.zeros(1, np.uint64)
-        lens = np.ascontiguousarray(in_len, np.uint64) if n else np.zeros(1, np.uint64)
-        total, ooff, ocap = B.layout(caps)
-        out = np.zeros(total, dtype=np.uint8)
-        out_len = np.zeros(max(n, 1), np.uint64)
-        in_used = np.zeros(max(n, 1), np.uint64)
-        status = np.zeros(max(n, 1), np.int32)
-        if (dict_off is None) != (dict_len is None):
-            raise ValueError("dict_off and dict_len: both or neither")
-        d_off = d_len = None
-        if dict_len is not None:
-            d_off = np.ascontiguousarray(dict_off, np.uint64) if n else np.zeros(1, np.uint64)
-            d_len = np.ascontiguousarray(dict_len, np.uint64) if n else np.zeros(1, np.uint64)
-            if n and (d_off.size != n or d_len.size != n):
-                raise ValueError("dict_off, dict_len: one entry per block")
-        if base.size == 0:
-            base = np.zeros(1, np.uint8)
-        p = lambda a: a.ctypes.data
-        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
-        args = [self._h, C.byref(b)]
-        aux = None
-        if flags:
-            aux = np.zeros(max(n, 1), np.uint32)
-            args.append(C.c_void_p(p(aux)))
-        args += [C.c_void_p(p(d_off) if d_off is not None else None), C.c_void_p(p(d_len) if d_len is not None else None)]
-        if dict_id is not None:
-            ids = np.array(list(dict_id) or [0], np.uint32)
-            args.append(C.c_void_p(p(ids)))
-        self._chk(getattr(N.lib(), fn_name)(*args))
-        return Result(B.unpack(out, ooff, out_len[:n]), out_len[:n], in_used[:n], status[:n], aux[:n] if aux is not None else None)
-
     def lz4_decode_shared(self, base, in_off, in_len, dict_off, dict_len, caps):
         """rcx_lz4_decode_shared_batch over a buffer the caller laid out: block i is base[in_off[i] : in_off[i] + in_len[i]] (base: a
         numpy uint8 array) and its matches may reach into base[dict_off[i] : dict_off[i] + dict_len[i]] (at most 65536 bytes, anywhere in
         the buffer; 0: none).  The results are those of a decode with the dictionary directly in front of the slot
         (rcx_lz4_decode_linked_batch with dict_len).  dict_off and dict_len None: lz4_decode_blocks' results."""
-        return self._shared_decode("rcx_lz4_decode_shared_batch", base, in_off, in_len, dict_off, dict_len, caps)
+        return self._shared("rcx_lz4_decode_shared_batch", base, in_off, in_len, dict_off, dict_len, caps)
 
     def lz4_decode_dict_blocks(self, blobs, dictionary, caps):
         """One LZ4 block per blob, decoded behind a dictionary (bytes for all blobs, or a list with one entry, bytes or None, per blob; the
@@ -312,7 +289,7 @@ class Context:
     def inflate_shared(self, base, in_off, in_len, dict_off, dict_len, caps):
         """rcx_inflate_shared_batch over a buffer the caller laid out, as lz4_decode_shared: dictionaries of at most 32768 bytes anywhere
         in the buffer; the results (aux: the flags) are inflate_hist_blocks' for the same dictionary directly in front of the slot."""
-        return self._shared_decode("rcx_inflate_shared_batch", base, in_off, in_len, dict_off, dict_len, caps, flags=True)
+        return self._shared("rcx_inflate_shared_batch", base, in_off, in_len, dict_off, dict_len, caps, flags=True)
 
     def inflate_dict_blocks(self, blobs, dictionary, caps):
         """One raw DEFLATE stream per blob, decoded behind a dictionary (bytes for all blobs, or a list with one entry, bytes or None,
@@ -332,18 +309,8 @@ class Context:
         base, off, lens = B.pack([b"".join(bytes(s) for s in c) for c in corpora])
         nsamples = np.array([len(c) for c in corpora] or [0], np.uint32)
         sample_len = np.array([len(s) for c in corpora for s in c] or [0], np.uint64)
-        total, ooff, ocap = B.layout([int(x) for x in sizes])
-        out = np.zeros(total, dtype=np.uint8)
-        out_len = np.zeros(max(n, 1), np.uint64)
-        in_used = np.zeros(max(n, 1), np.uint64)
-        status = np.zeros(max(n, 1), np.int32)
-        if not n:
-            off = lens = ooff = ocap = np.zeros(1, np.uint64)
-        p = lambda a: a.ctypes.data
-        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
-        self._chk(N.lib().rcx_dict_train_batch(self._h, C.byref(b), C.c_void_p(p(nsamples)), C.c_void_p(p(sample_len)), int(k), int(d), int(f)))
-        Result([], out_len[:n], in_used[:n], status[:n], None).check()
-        return B.unpack(out, ooff, out_len[:n])
+        res = self._batch("rcx_dict_train_batch", base, off, lens, _slots([int(x) for x in sizes]), nsamples, sample_len, int(k), int(d), int(f))
+        return res.check().outputs
 
     def train_dictionary(self, samples, size, k=256, d=8, f=20):
         """train_dictionaries for one corpus -> bytes"""
@@ -361,8 +328,8 @@ class Context:
             return self._run_host("rcx_zlib_decode_batch", blobs, caps, extra_out=True)
         if shared:
             base, off, lens, d_off, d_len, dicts = _pack_shared(blobs, zdict, 32768)
-            return self._shared_decode("rcx_zlib_decode_shared_batch", base, off, lens, d_off, d_len, caps, flags=True,
-                                       dict_id=[_adler32(d) for d in dicts])
+            return self._shared("rcx_zlib_decode_shared_batch", base, off, lens, d_off, d_len, caps, flags=True,
+                                dict_id=[_adler32(d) for d in dicts])
         dicts = _per_blob(zdict, len(blobs))
         return self._inflate_hist(blobs, dicts, caps, [_adler32(d) for d in dicts])
 
@@ -388,18 +355,13 @@ class Context:
                 out[int(ooff[i]) - len(h):int(ooff[i])] = np.frombuffer(h, np.uint8)
         ocap = np.array(list(caps) or [0], np.uint64)
         hl = np.array([len(h) for h in hists] or [0], np.uint64)
-        out_len = np.zeros(max(n, 1), np.uint64)
-        in_used = np.zeros(max(n, 1), np.uint64)
-        status = np.zeros(max(n, 1), np.int32)
         flags = np.zeros(max(n, 1), np.uint32)
-        p = lambda a: a.ctypes.data
-        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
         if dict_id is None:
-            self._chk(N.lib().rcx_inflate_hist_batch(self._h, C.byref(b), C.c_void_p(p(flags)), C.c_void_p(p(hl))))
+            res = self._batch("rcx_inflate_hist_batch", base, off, lens, (out, ooff, ocap), flags, hl)
         else:
-            ids = np.array(list(dict_id) or [0], np.uint32)
-            self._chk(N.lib().rcx_zlib_decode_dict_batch(self._h, C.byref(b), C.c_void_p(p(flags)), C.c_void_p(p(hl)), C.c_void_p(p(ids))))
-        return Result(B.unpack(out, ooff[:n], out_len[:n]), out_len[:n], in_used[:n], status[:n], flags[:n])
+            res = self._batch("rcx_zlib_decode_dict_batch", base, off, lens, (out, ooff, ocap), flags, hl, np.array(list(dict_id) or [0], np.uint32))
+        res.aux = flags[:n]
+        return res
 
     def adler32(self, blobs):
         return self._run_host("rcx_adler32_batch", blobs, None, extra_out=True, needs_out=False)
@@ -441,7 +403,7 @@ class Context:
             d_off = d_len = None
         else:
             base, off, lens, d_off, d_len, _ = _pack_shared(blobs, dictionary, 1 << 32)
-        res = self._shared_decode("rcx_zstd_decode_batch", base, off, lens, d_off, d_len, caps)
+        res = self._shared("rcx_zstd_decode_batch", base, off, lens, d_off, d_len, caps)
         res.outputs = [o if st == 0 else b"" for o, st in zip(res.outputs, res.status)]     # (out_len of a slot too small is a size, not bytes)
         return res
 
@@ -449,12 +411,8 @@ class Context:
         """XXH64 of every blob (rcx_xxh64_batch; extension) -> a uint64 array.  A Zstandard frame's content checksum is the low 32 bits."""
         n = len(blobs)
         base, off, lens = B.pack(blobs)
-        status = np.zeros(max(n, 1), np.int32)
-        in_used = np.zeros(max(n, 1), np.uint64)
         hashes = np.zeros(max(n, 1), np.uint64)
-        p = lambda a: a.ctypes.data
-        b = N.Batch(p(base), p(off), p(lens), None, None, None, None, p(in_used), p(status), n, N.MEM_HOST)
-        self._chk(N.lib().rcx_xxh64_batch(self._h, C.byref(b), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_void_p(p(hashes))))
+        self._batch("rcx_xxh64_batch", base, off, lens, None, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), hashes)
         return hashes[:n]
 
     def _deflate_encode(self, fn, blobs, caps, framing, level):
@@ -480,7 +438,7 @@ class Context:
             base, off, lens, d_off, d_len, dicts = _pack_shared(blobs, zdict, 32768)
             if caps is None:
                 caps = [deflate_bound(n) + 10 for n in lens]
-            return self._shared("rcx_zlib_encode_shared_batch", base, off, lens, d_off, d_len, level, caps, [_adler32(d) for d in dicts])
+            return self._shared("rcx_zlib_encode_shared_batch", base, off, lens, d_off, d_len, caps, level, dict_id=[_adler32(d) for d in dicts])
         dicts = _per_blob(zdict, len(blobs))
         base, off, hl = _pack_hist(blobs, dicts, 32768)
         return self._deflate_hist(base, off, [len(b) for b in blobs], hl, level, caps, [_adler32(d) for d in dicts])
@@ -501,30 +459,10 @@ class Context:
         return self.deflate_encode_hist(base, off, [len(b) for b in blobs], hl, level, caps)
 
     def _deflate_hist(self, base, in_off, in_len, hist_len, level, caps, dict_id):
-        n = len(in_off)
-        off = np.ascontiguousarray(in_off, np.uint64) if n else np.zeros(1, np.uint64)
-        lens = np.ascontiguousarray(in_len, np.uint64) if n else np.zeros(1, np.uint64)
         if caps is None:
-            caps = [deflate_bound(int(l)) + (10 if dict_id is not None else 0) for l in lens[:n]]
-        total, ooff, ocap = B.layout(caps)
-        out = np.zeros(total, dtype=np.uint8)
-        out_len = np.zeros(max(n, 1), np.uint64)
-        in_used = np.zeros(max(n, 1), np.uint64)
-        status = np.zeros(max(n, 1), np.int32)
-        hist = np.ascontiguousarray(hist_len, np.uint64) if hist_len is not None else None
-        if hist is not None and hist.size != n:
-            raise ValueError("hist_len: one entry per block")
-        if base.size == 0:
-            base = np.zeros(1, np.uint8)
-        p = lambda a: a.ctypes.data
-        b = N.Batch(p(base), p(off), p(lens), p(out), p(ooff), p(ocap), p(out_len), p(in_used), p(status), n, N.MEM_HOST)
-        hp = C.c_void_p(p(hist) if hist is not None and n else None)
-        if dict_id is None:
-            self._chk(N.lib().rcx_deflate_encode_hist_batch(self._h, C.byref(b), int(level), hp))
-        else:
-            ids = np.array(list(dict_id) or [0], np.uint32)
-            self._chk(N.lib().rcx_zlib_encode_dict_batch(self._h, C.byref(b), int(level), hp, C.c_void_p(p(ids))))
-        return Result(B.unpack(out, ooff, out_len[:n]), out_len[:n], in_used[:n], status[:n], None)
+            caps = [deflate_bound(int(l)) + (10 if dict_id is not None else 0) for l in in_len]
+        return self._encode_hist("rcx_deflate_encode_hist_batch" if dict_id is None else "rcx_zlib_encode_dict_batch", base, in_off, in_len, hist_len,
+                                 level, caps, dict_id)
 
     def gzip_encode(self, blobs, caps=None, level=1):
         """One gzip member (RFC 1952, no optional header fields, MTIME 0, OS 255) per blob; caps default to the DEFLATE bound + 18."""

@@ -77,22 +77,8 @@ def decode_many(blobs, ctx=None, return_exceptions=False, with_used=False):
     n = len(blobs)
     if n == 0:
         return []
-    sizes = ctx.bzip2_decode(blobs, [0] * n)
-    results = [None] * n
-    todo = []
-    for i in range(n):
-        st = int(sizes.status[i])
-        if st == N.E_OUTPUT_TOO_SMALL:
-            todo.append(i)
-        elif st == 0:                                       # a file that decodes to nothing
-            results[i] = (b"", int(sizes.in_used[i])) if with_used else b""
-        else:
-            results[i] = _error(i, st)
-    if todo:
-        res = ctx.bzip2_decode([blobs[i] for i in todo], [int(sizes.out_len[i]) for i in todo])
-        for k, i in enumerate(todo):
-            st = int(res.status[k])
-            results[i] = _error(i, st) if st else ((res.outputs[k], int(res.in_used[k])) if with_used else res.outputs[k])
+    got = _compress._exact_retry(lambda idx, caps: ctx.bzip2_decode([blobs[i] for i in idx], caps), [0] * n)      # (capacities of 0: a size query)
+    results = [_error(i, st) if st else ((out, used) if with_used else out) for i, (st, out, used) in enumerate(got)]
     if not return_exceptions and any(isinstance(r, Exception) for r in results):
         raise FilesFailed(results)
     return results
@@ -124,21 +110,19 @@ def encode_many(datas, level=9, ctx=None):
     datas = [bytes(d) for d in datas]
     if not datas:
         return []
-    res = ctx.bzip2_encode(datas, [len(d) + len(d) // 64 + 1024 for d in datas], level)
-    out = list(res.outputs)
-    todo = []
-    for i, st in enumerate(res.status[:len(datas)]):
-        if int(st) == N.E_OUTPUT_TOO_SMALL:
-            todo.append(i)
-        elif int(st):
-            raise CompressError(int(st), "bzip2 file %d: %s" % (i, N.lib().rcx_status_string(int(st)).decode()))
-    if todo:
-        again = ctx.bzip2_encode([datas[i] for i in todo], [int(res.out_len[i]) for i in todo], level)
-        for k, i in enumerate(todo):
-            if int(again.status[k]):
-                raise CompressError(int(again.status[k]), "bzip2 file %d: %s" % (i, N.lib().rcx_status_string(int(again.status[k])).decode()))
-            out[i] = again.outputs[k]
-    return out
+    def check(i, st, but=0):
+        if st and st != but:
+            raise CompressError(st, "bzip2 file %d: %s" % (i, N.lib().rcx_status_string(st).decode()))
+
+    def call(idx, caps):
+        res = ctx.bzip2_encode([datas[i] for i in idx], caps, level)
+        for i, st in zip(idx, res.status):                  # a file that fails ends it at once: nothing is encoded again for the others
+            check(i, int(st), but=N.E_OUTPUT_TOO_SMALL)
+        return res
+    got = _compress._exact_retry(call, [len(d) + len(d) // 64 + 1024 for d in datas])
+    for i, (st, _, _) in enumerate(got):
+        check(i, st)
+    return [out for _, out, _ in got]
 
 
 class Encoder:

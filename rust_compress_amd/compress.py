@@ -128,6 +128,21 @@ def _grow_caps(call, first_cap, limit=MAX_BLOCK):
         return res
 
 
+def _exact_retry(call, first_caps):
+    """_grow_caps' counterpart for the entry points that SIZE (bzip2, Zstandard): a slot too small answers RCX_E_OUTPUT_TOO_SMALL with the
+    exact size in out_len, so the files that did not fit are handed over once more, with exactly that.  call(indices, caps) -> the Result
+    for those files; first_caps: one capacity per file, the caller's policy.  -> per file (status, output, in_used), after two calls at
+    the most."""
+    res = call(list(range(len(first_caps))), list(first_caps))
+    got = [(int(st), o, int(u)) for st, o, u in zip(res.status, res.outputs, res.in_used)]
+    todo = [i for i, g in enumerate(got) if g[0] == N.E_OUTPUT_TOO_SMALL]
+    if todo:
+        again = call(todo, [int(res.out_len[i]) for i in todo])
+        for k, i in enumerate(todo):
+            got[i] = (int(again.status[k]), again.outputs[k], int(again.in_used[k]))
+    return got
+
+
 class _BufferedDecoder:
     """Serves self._out through read(n); subclasses fill it in _decode_all() on first use and set self.consumed when
     their stream ends before the input does (the rest goes back to the reader)."""

@@ -90,25 +90,14 @@ class FramesFailed(CompressError):
         CompressError.__init__(self, self.errors[0].status, "%d of %d blobs failed; the first: %s" % (len(self.errors), len(results), self.errors[0]))
 
 
-def _p(a):
-    return a.ctypes.data if a is not None else None
-
-
 def xxh32_many(base, offs, lens, seed=0, ctx=None):
     """XXH32 of base[offs[i] : offs[i] + lens[i]] for every i in one rcx_xxh32_batch call -> numpy uint32 array.  base: a numpy uint8 array."""
     n = len(offs)
     if n == 0:
         return np.zeros(0, np.uint32)
     ctx = ctx or _compress.context()
-    off = np.ascontiguousarray(offs, np.uint64)
-    ln = np.ascontiguousarray(lens, np.uint64)
-    if base.size == 0:
-        base = np.zeros(1, np.uint8)
-    status = np.zeros(n, np.int32)
-    used = np.zeros(n, np.uint64)
     h = np.zeros(n, np.uint32)
-    b = N.Batch(_p(base), _p(off), _p(ln), None, None, None, None, _p(used), _p(status), n, N.MEM_HOST)
-    ctx._chk(N.lib().rcx_xxh32_batch(ctx._h, C.byref(b), C.c_uint32(seed), C.c_void_p(_p(h))))
+    ctx._batch("rcx_xxh32_batch", base, offs, lens, None, C.c_uint32(seed), h)
     return h
 
 
@@ -335,15 +324,10 @@ def decode_frames(blobs, dictionary=None, verify=True, return_exceptions=False, 
         d = np.frombuffer(dct, np.uint8)
         for at in dict_at:
             out[at:at + d.size] = d
-    out_len = np.zeros(max(n, 1), np.uint64)
-    status = np.zeros(max(n, 1), np.int32)
     if n:
-        a_in_off, a_in_len = np.array(in_off, np.uint64), np.array(in_len, np.uint64)
-        a_out_off, a_out_cap = np.array(out_off, np.uint64), np.array(out_cap, np.uint64)
-        a_link, a_dlen = np.array(link, np.uint8), np.array(dlen, np.uint64)
-        in_used = np.zeros(n, np.uint64)
-        b = N.Batch(_p(inbuf), _p(a_in_off), _p(a_in_len), _p(out), _p(a_out_off), _p(a_out_cap), _p(out_len), _p(in_used), _p(status), n, N.MEM_HOST)
-        ctx._chk(N.lib().rcx_lz4_decode_linked_batch(ctx._h, C.byref(b), C.c_void_p(_p(a_link)), C.c_void_p(_p(a_dlen))))
+        res = ctx._batch("rcx_lz4_decode_linked_batch", inbuf, in_off, in_len, (out, out_off, out_cap), np.array(link, np.uint8), np.array(dlen, np.uint64),
+                         unpack=False)
+        out_len, status = res.out_len, res.status
 
     def head_of(j):
         while link[j]:

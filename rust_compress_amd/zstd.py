@@ -12,6 +12,7 @@ dictionary: raw content (what train_dictionary returns), history in front of eve
 formatted dictionary, which is not supported.  There is no CPU path."""
 from . import _native as N
 from . import compress as _compress
+from .api import _per_blob
 from .compress import CompressError
 
 MAGIC = 0xFD2FB528
@@ -113,30 +114,16 @@ def decode_many(blobs, dictionary=None, ctx=None, return_exceptions=False, with_
     n = len(blobs)
     if n == 0:
         return []
-    dicts = dictionary if isinstance(dictionary, (list, tuple)) else [dictionary] * n
+    dicts = None if dictionary is None else _per_blob(dictionary, n)
     # a declared size is taken for the first call's slot only where it is plausible for the file's length (an RLE block makes 2 MiB of
     # 4 bytes, a match 64 KiB of a few bits: 64 MiB or 1024 times the file, whichever is more); beyond that the call sizes the file
     # itself, so a few hostile bytes cannot ask for a slot of 4 GiB before anything has been checked
     def first_cap(b):
         size = declared_size(b) or 0
         return size if size <= max(64 << 20, 1024 * len(b)) else 0
-    first = ctx.zstd_decode(blobs, [first_cap(b) for b in blobs], dictionary)
-    results = [None] * n
-    todo = []
-    for i in range(n):
-        st = int(first.status[i])
-        if st == N.E_OUTPUT_TOO_SMALL:
-            todo.append(i)
-        elif st == 0:
-            results[i] = (first.outputs[i], int(first.in_used[i])) if with_used else first.outputs[i]
-        else:
-            results[i] = _error(i, st)
-    if todo:
-        res = ctx.zstd_decode([blobs[i] for i in todo], [int(first.out_len[i]) for i in todo],
-                              None if dictionary is None else [dicts[i] for i in todo])
-        for k, i in enumerate(todo):
-            st = int(res.status[k])
-            results[i] = _error(i, st) if st else ((res.outputs[k], int(res.in_used[k])) if with_used else res.outputs[k])
+    got = _compress._exact_retry(lambda idx, caps: ctx.zstd_decode([blobs[i] for i in idx], caps, dicts and [dicts[i] for i in idx]),
+                                 [first_cap(b) for b in blobs])
+    results = [_error(i, st) if st else ((out, used) if with_used else out) for i, (st, out, used) in enumerate(got)]
     if not return_exceptions and any(isinstance(r, Exception) for r in results):
         raise FilesFailed(results)
     return results

@@ -2,32 +2,20 @@
 they call, on the wave64 simulator (TEST INFRASTRUCTURE)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+from wavesim.build import build_sim
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 OUT = os.path.join(HERE, "sim_bzip2", "build", "libsim_bzip2.so")
 KINDS = {0: "block", 1: "end", 2: "head"}
 _lib = None
 
 
 def build():
-    src = os.path.join(HERE, "sim_bzip2", "sim_bzip2.cpp")
-    ws = os.path.join(HERE, "wavesim")
-    csrc = os.path.join(ROOT, "rust_compress_amd", "csrc")
-    deps = [src, os.path.join(ws, "wavesim.h"), os.path.join(ws, "wavesim.cpp")] + \
-           [os.path.join(csrc, f) for f in ("k_bzip2.hip", "k_bwt_inverse.hip", "k_crc32.hip", "rcx_dev.h", "rcx_plan.h")]
-    if os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in deps):
-        return OUT
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    tmp = OUT + ".%d" % os.getpid()
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-x", "c++", "-include", os.path.join(ws, "wavesim.h"),
-                           "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-unused-variable", "-Wno-unused-but-set-variable", "-Wno-attributes",
-                           "-o", tmp, src, os.path.join(ws, "wavesim.cpp")])
-    os.replace(tmp, OUT)
-    return OUT
+    return build_sim(OUT, os.path.join(HERE, "sim_bzip2", "sim_bzip2.cpp"),
+                     ("k_bzip2.hip", "k_bwt_inverse.hip", "k_crc32.hip", "rcx_dev.h", "rcx_plan.h"), ("-Wno-unused-but-set-variable",))
 
 
 def lib():

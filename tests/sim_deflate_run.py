@@ -1,31 +1,18 @@
 """Builds and drives tests/sim_deflate/sim_deflate.cpp: the DEFLATE encoder kernels on the wave64 simulator (TEST INFRASTRUCTURE)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+from wavesim.build import build_sim
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 OUT = os.path.join(HERE, "sim_deflate", "build", "libsim_deflate.so")
 _lib = None
 
 
 def build():
-    src = os.path.join(HERE, "sim_deflate", "sim_deflate.cpp")
-    ws = os.path.join(HERE, "wavesim")
-    deps = [src, os.path.join(ws, "wavesim.h"), os.path.join(ws, "wavesim.cpp"),
-            os.path.join(ROOT, "rust_compress_amd", "csrc", "k_deflate_encode.hip"), os.path.join(ROOT, "rust_compress_amd", "csrc", "lz_match.h"),
-            os.path.join(ROOT, "rust_compress_amd", "csrc", "rcx_dev.h")]
-    if os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in deps):
-        return OUT
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    tmp = OUT + ".%d" % os.getpid()
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-x", "c++", "-include", os.path.join(ws, "wavesim.h"),
-                           "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-unused-variable", "-Wno-attributes",
-                           "-o", tmp, src, os.path.join(ws, "wavesim.cpp")])
-    os.replace(tmp, OUT)
-    return OUT
+    return build_sim(OUT, os.path.join(HERE, "sim_deflate", "sim_deflate.cpp"), ("k_deflate_encode.hip", "lz_match.h", "rcx_dev.h"))
 
 
 def lib():

@@ -6,6 +6,8 @@ import subprocess
 
 import numpy as np
 
+from wavesim.build import build_sim
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SEG = 65536
@@ -20,24 +22,10 @@ def _out(family):
 
 
 def build(family):
-    src = os.path.join(HERE, "sim_dict_shared", "sim_dict_shared.cpp")
-    ws = os.path.join(HERE, "wavesim")
-    csrc = os.path.join(ROOT, "rust_compress_amd", "csrc")
-    deps = [src, os.path.join(ws, "wavesim.h"), os.path.join(ws, "wavesim.cpp")] + \
-           [os.path.join(csrc, f) for f in ("k_lz4_hc.hip", "k_lz4_hc_dict.hip", "k_deflate_encode.hip", "k_deflate_hc.hip",
-                                            "k_deflate_hc_hist.hip", "k_deflate_hc_dict.hip", "k_inflate.hip", "k_crc32.hip", "lz_dict.h",
-                                            "lz_match.h", "rcx_dev.h", "rcx_plan.h")]
-    out = _out(family)
-    if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
-        return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    tmp = out + ".%d" % os.getpid()
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-x", "c++", "-include", os.path.join(ws, "wavesim.h"),
-                           "-DSIM_LZ4" if family == "lz4" else "-DSIM_DEFLATE",
-                           "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-unused-variable", "-Wno-attributes",
-                           "-o", tmp, src, os.path.join(ws, "wavesim.cpp")])
-    os.replace(tmp, out)
-    return out
+    return build_sim(_out(family), os.path.join(HERE, "sim_dict_shared", "sim_dict_shared.cpp"),
+                     ("k_lz4_hc.hip", "k_lz4_hc_dict.hip", "k_deflate_encode.hip", "k_deflate_hc.hip", "k_deflate_hc_hist.hip", "k_deflate_hc_dict.hip",
+                      "k_inflate.hip", "k_crc32.hip", "lz_dict.h", "lz_match.h", "rcx_dev.h", "rcx_plan.h"),
+                     ("-DSIM_LZ4" if family == "lz4" else "-DSIM_DEFLATE",))
 
 
 def lib(family):

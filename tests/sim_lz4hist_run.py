@@ -2,12 +2,12 @@
 INFRASTRUCTURE)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+from wavesim.build import build_sim
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 OUT = os.path.join(HERE, "sim_lz4hist", "build", "libsim_lz4hist.so")
 SEG = 65536
 ELEN = SEG + 64
@@ -15,20 +15,7 @@ _lib = None
 
 
 def build():
-    src = os.path.join(HERE, "sim_lz4hist", "sim_lz4hist.cpp")
-    ws = os.path.join(HERE, "wavesim")
-    csrc = os.path.join(ROOT, "rust_compress_amd", "csrc")
-    deps = [src, os.path.join(ws, "wavesim.h"), os.path.join(ws, "wavesim.cpp")] + \
-           [os.path.join(csrc, f) for f in ("k_lz4_hc.hip", "k_lz4_hc_hist.hip", "lz_match.h", "rcx_dev.h")]
-    if os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in deps):
-        return OUT
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    tmp = OUT + ".%d" % os.getpid()
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-x", "c++", "-include", os.path.join(ws, "wavesim.h"),
-                           "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-unused-variable", "-Wno-attributes",
-                           "-o", tmp, src, os.path.join(ws, "wavesim.cpp")])
-    os.replace(tmp, OUT)
-    return OUT
+    return build_sim(OUT, os.path.join(HERE, "sim_lz4hist", "sim_lz4hist.cpp"), ("k_lz4_hc.hip", "k_lz4_hc_hist.hip", "lz_match.h", "rcx_dev.h"))
 
 
 def lib():
