@@ -350,29 +350,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_adler32(rcx_kargs a)
 #ifndef INF3_OCC
 #define INF3_OCC 6
 #endif
-template <int SPW, int LG, int MINW> __global__ __launch_bounds__(64, MINW) void k_inflate2(rcx_kargs a, int zlib);
 template <int CB, bool SPEC = false, bool ADLER = false, bool MIRROR = false> __global__ __launch_bounds__(64, INF3_OCC) void k_inflate3(rcx_kargs a, int zlib);
 __global__ void k_zlib_tail3(rcx_kargs a, const uint32_t* adler);
 template <int WAVES> __global__ void k_adler32(rcx_kargs a);
 
-// one lane per stream (k_inflate2); `flags`: bit 0 zlib framing, bit 1 only the blocks k_inflate3 handed back
-static void launch_inflate2(hipStream_t s, rcx_kargs& k, int flags, int v)
-{
-    // streams per wave: the largest of 32/16/8 that still gives 2048 waves (measured: benchmarks/inflate_spw_sweep.py;
-    // full waves are never the fastest); variants 2..5 pin it (A/B)
-    const uint32_t n = k.nblocks;
-    int spw = v == 2 ? 64 : v == 3 ? 32 : v == 4 ? 16 : v == 5 ? 8 : (n >= 32u * 2048u ? 32 : n >= 16u * 2048u ? 16 : 8);
-    const int z = flags;
-#ifdef RCX_AB_VARIANTS
-    if (v == 6) { hipLaunchKernelGGL((k_inflate2<16, 4, 4>), dim3((n + 15) / 16), dim3(16), 0, s, k, z); return; }
-    if (v == 7) { hipLaunchKernelGGL((k_inflate2<32, 5, 3>), dim3((n + 31) / 32), dim3(32), 0, s, k, z); return; }
-    if (v == 8) { hipLaunchKernelGGL((k_inflate2<16, 4, 3>), dim3((n + 15) / 16), dim3(16), 0, s, k, z); return; }
-    if (spw == 64) { hipLaunchKernelGGL((k_inflate2<64, 6, 1>), dim3((n + 63) / 64), dim3(64), 0, s, k, z); return; }
-#endif
-    if (spw >= 32) hipLaunchKernelGGL((k_inflate2<32, 5, 1>), dim3((n + 31) / 32), dim3(32), 0, s, k, z);
-    else if (spw == 16) hipLaunchKernelGGL((k_inflate2<16, 4, 1>), dim3((n + 15) / 16), dim3(16), 0, s, k, z);
-    else hipLaunchKernelGGL((k_inflate2<8, 3, 1>), dim3((n + 7) / 8), dim3(8), 0, s, k, z);
-}
+// one lane per stream (k_inflate2.hip, with the streams-per-wave choice its three kernels share)
+static void launch_inflate2(hipStream_t s, rcx_kargs& k, int flags, int v);
 
 static constexpr uint32_t INF3_MAX_STREAMS = 0xffffffffu;   // every batch size measured (1024 .. 65536 streams) is faster wave-per-stream
 // scratch the default path wants: Adler-32 values (zlib) and a stand-in for a null in_used

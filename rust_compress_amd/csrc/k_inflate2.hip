@@ -14,6 +14,10 @@
 //     gather per 16 bytes (the source is always drained: distance >= 112);
 //   * symbols are u8 + a 9th-bit bitmap: 31 KB of LDS per wave -> 5 waves per CU.
 // Reference citations as in k_inflate.hip (src/flate.rs:83-146, :195-450; src/zlib.rs:55-126).
+//
+// This file holds the ONE symbol loop and the table builders of the lane-per-stream decoders.  k_inflate_hist.hip (history in front
+// of the slot) and k_inflate_dict.hip (shared dictionaries) have kernels of their own and call f2_stored / f2_fixed / f2_dynamic here;
+// f2_codes takes where a far match's bytes come from as a source policy (F2SlotSrc / F2DictSrc), a compile-time choice.
 #include "rcx_dev.h"
 
 #define F2_W 128u                 /* ring bytes per lane */
@@ -177,22 +181,60 @@ struct F2 {
     }
 };
 
-__device__ const uint16_t F2_EXTRALENS[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51,
-                                              59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-__device__ const uint8_t F2_EXTRABITS[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4,
-                                             4, 5, 5, 5, 5, 0};
-__device__ const uint16_t F2_EXTRADIST[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385,
-                                              513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
-__device__ const uint8_t F2_EXTRADBITS[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9,
-                                              10, 10, 11, 11, 12, 12, 13, 13};
 __device__ const uint8_t F2_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+
+// f2_codes' SOURCE POLICY, passed by value: what lies behind the bytes decoded so far.  It answers three questions -- how many bytes
+// a distance may reach back (reach), the 16 bytes of a far source (distance >= F2_NEAR: drained long ago) at position src (gather),
+// and the first such gather, started when the match is decoded (early: false leaves it to gather).
+// F2SlotSrc: nothing but the stream itself, F2::out[0, end) -- k_inflate2, and k_inflate_hist, whose virtual stream begins with its
+// history.  (A far source ends 96 bytes or more below end, so its 16 bytes always lie below cap; the byte-wise tail is kept as a guard.)
+struct F2SlotSrc {
+    __device__ __forceinline__ uint64_t reach(const F2& s) const { return s.end; }
+    __device__ __forceinline__ rcx_u32x4 gather(const F2& s, uint64_t src) const
+    {
+        if (src + 16 <= s.cap) return *(const rcx_u32x4_u*)(s.out + src);
+        uint32_t t4[4] = {0, 0, 0, 0};
+        for (uint32_t i = 0; i < 16 && src + i < s.end; i++) t4[i >> 2] |= (uint32_t)s.out[src + i] << (8 * (i & 3));
+        return rcx_u32x4{t4[0], t4[1], t4[2], t4[3]};
+    }
+    __device__ __forceinline__ bool early(const F2& s, uint64_t src, rcx_u32x4& g) const
+    {
+        if (src + 16 > s.cap) return false;
+        g = *(const rcx_u32x4_u*)(s.out + src);
+        return true;
+    }
+};
+// F2DictSrc: a dictionary of D bytes at `dict` stands for the positions -D .. -1 (k_inflate_dict.hip: POSITIONS ARE THE SLOT'S).  A
+// position below 0 is dict[D + position], anything else the slot's; a gather that straddles position 0 is put together byte by byte,
+// so no 16-byte load crosses the dictionary's last byte or begins below its first.  src arrives as end - distance, wrapped below 0.
+struct F2DictSrc {
+    const uint8_t* dict; uint32_t D;
+    __device__ __forceinline__ uint64_t reach(const F2& s) const { return s.end + D; }
+    __device__ __forceinline__ rcx_u32x4 gather(const F2& s, uint64_t at) const      // src + D >= 0: the distance rule
+    {
+        const int64_t src = (int64_t)at;
+        if (src >= 0 && (uint64_t)src + 16 <= s.cap) return *(const rcx_u32x4_u*)(s.out + src);
+        if (src + 16 <= 0) return *(const rcx_u32x4_u*)(dict + ((int64_t)D + src));
+        uint32_t t4[4] = {0, 0, 0, 0};                                         // straddles position 0
+        for (int i = 0; i < 16; i++) {
+            const int64_t p = src + i;
+            uint32_t x = 0;
+            if (p < 0) x = dict[(int64_t)D + p];
+            else if ((uint64_t)p < s.end) x = s.out[p];
+            t4[i >> 2] |= x << (8 * (i & 3));
+        }
+        return rcx_u32x4{t4[0], t4[1], t4[2], t4[3]};
+    }
+    __device__ __forceinline__ bool early(const F2& s, uint64_t src, rcx_u32x4& g) const { g = gather(s, src); return true; }
+};
 
 // Decoder::codes, flate.rs:262-341, as a per-lane state machine.  The 64 lanes of a wave run 64 different
 // streams, so the loop body is written to be executed by everybody: ONE "emit up to 4 pending bytes" path
 // (literal, ring source with period handling for distances 1-3, or 4 bytes of a 16-byte far gather) and ONE
 // "decode the next symbol" path.  (rocprof on the straightforward per-symbol loop: ~1250 wave instructions
 // per decoded symbol, because every lane's literal waited for every other lane's inlined copy/drain code.)
-__device__ int f2_codes(F2& s, const F2Huff& HL, const F2Huff& HD)
+template <class SRC>
+__device__ int f2_codes(F2& s, const F2Huff& HL, const F2Huff& HD, const SRC from)
 {
     uint32_t pend = 0, dd = 0, w = 0;          // pending bytes of the current symbol; dd == 0: the literal in w
     rcx_u32x4 g = {0, 0, 0, 0};                // far-match gather buffer
@@ -206,16 +248,11 @@ __device__ int f2_codes(F2& s, const F2Huff& HL, const F2Huff& HD)
                 const uint32_t i1 = dd > 1 ? 1u : 0u;
                 const uint32_t i2 = dd > 2 ? 2u : 0u;
                 const uint32_t i3 = dd > 3 ? 3u : (dd == 2 ? 1u : 0u);
-                const uint64_t sp = s.end - dd;
+                const uint64_t sp = s.end - dd;                            // (below position 0, a dictionary's: wraps, the same ring byte)
                 const uint32_t b0 = *s.RB(sp), b1 = *s.RB(sp + i1), b2 = *s.RB(sp + i2), b3 = *s.RB(sp + i3);
                 w4 = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
             } else {                                                       // drained source: 16-byte gather, 4 bytes a step
-                if (gpos >= 16) {
-                    const uint64_t src = s.end - dd;
-                    if (src + 16 <= s.cap) g = *(const rcx_u32x4_u*)(s.out + src);
-                    else { uint32_t t4[4] = {0, 0, 0, 0}; for (uint32_t i = 0; i < 16 && src + i < s.end; i++) t4[i >> 2] |= (uint32_t)s.out[src + i] << (8 * (i & 3)); g = rcx_u32x4{t4[0], t4[1], t4[2], t4[3]}; }
-                    gpos = 0;
-                }
+                if (gpos >= 16) { g = from.gather(s, s.end - dd); gpos = 0; }
                 w4 = gpos == 0 ? g[0] : gpos == 4 ? g[1] : gpos == 8 ? g[2] : g[3];
                 gpos += 4;
             }
@@ -259,14 +296,12 @@ __device__ int f2_codes(F2& s, const F2Huff& HL, const F2Huff& HD)
             st = s.bits(db, x);
             if (st) return st;
             const uint32_t dist = dbase + x;
-            const uint64_t hist = s.end < 32768u ? s.end : 32768u;         // output.len(), :314
-            if (dist > hist) return RCX_E_INVALID_HUFFMAN_CODE;
+            const uint64_t have = from.reach(s);                           // output.len(), :314, with what lies behind it
+            if (dist > (have < 32768u ? have : 32768u)) return RCX_E_INVALID_HUFFMAN_CODE;
             if (len > s.cap - s.end) return RCX_E_OUTPUT_TOO_SMALL;
             pend = len; dd = dist; gpos = 16;
-            if (dist >= F2_NEAR && s.end - dist + 16 <= s.cap) {           // start the first gather now: its latency
-                g = *(const rcx_u32x4_u*)(s.out + (s.end - dist));        // overlaps the other lanes' work
-                gpos = 0;
-            }
+            // start the first gather now: its latency overlaps the other lanes' work
+            if (dist >= F2_NEAR && from.early(s, s.end - dist, g)) gpos = 0;
         } else {
             return RCX_E_INVALID_HUFFMAN_CODE;                             // :336
         }
@@ -289,7 +324,8 @@ __device__ int f2_stored(F2& s)
     return RCX_OK;
 }
 
-__device__ int f2_fixed(F2& s, F2Huff& HL, F2Huff& HD, uint8_t* lens)
+template <class SRC>
+__device__ int f2_fixed(F2& s, F2Huff& HL, F2Huff& HD, uint8_t* lens, const SRC from)
 {
     for (unsigned i = 0; i < 144; i++) lens[i] = 8;
     for (unsigned i = 144; i < 256; i++) lens[i] = 9;
@@ -299,11 +335,12 @@ __device__ int f2_fixed(F2& s, F2Huff& HL, F2Huff& HD, uint8_t* lens)
     s.construct<0>(HL, lens, 288, e);
     for (unsigned i = 0; i < 30; i++) lens[i] = 5;
     s.construct<1>(HD, lens, 30, e);
-    return f2_codes(s, HL, HD);
+    return f2_codes(s, HL, HD, from);
 }
 
 // Decoder::dynamic, flate.rs:397-450
-__device__ int f2_dynamic(F2& s, F2Huff& HL, F2Huff& HD, uint8_t* lens)
+template <class SRC>
+__device__ int f2_dynamic(F2& s, F2Huff& HL, F2Huff& HD, uint8_t* lens, const SRC from)
 {
     uint32_t x;
     int st;
@@ -350,7 +387,7 @@ __device__ int f2_dynamic(F2& s, F2Huff& HL, F2Huff& HD, uint8_t* lens)
     if (i > hlit + hdist) return RCX_E_INVALID_HUFFMAN_TREE_HEADER;        // :442
     if ((st = s.construct<0>(HL, lens, hlit, e))) return st;               // :445-446
     if ((st = s.construct<1>(HD, lens + hlit, hdist, e))) return st;       // :447-448
-    return f2_codes(s, HL, HD);
+    return f2_codes(s, HL, HD, from);
 }
 
 // LDS per stream: lsym 288 B + 9th-bit bitmap 9 words + dsym 32 B + ring 128 B = 484 B.
@@ -400,8 +437,8 @@ __global__ __launch_bounds__(64, MINW) void k_inflate2(rcx_kargs a, int zlib)
         if (x == 1) eof = true;                                            // :198
         if ((st = s.bits(2, x))) break;                                    // :199
         if (x == 0) st = f2_stored(s);
-        else if (x == 1) st = f2_fixed(s, HL, HD, lens);
-        else if (x == 2) st = f2_dynamic(s, HL, HD, lens);
+        else if (x == 1) st = f2_fixed(s, HL, HD, lens, F2SlotSrc{});
+        else if (x == 2) st = f2_dynamic(s, HL, HD, lens, F2SlotSrc{});
         else st = RCX_E_INVALID_BLOCK_CODE;                                // :203
         if (!st && s.end == before && !eof) flags |= RCX_W_EMPTY_BLOCK_MIDSTREAM;   // :474-476 quirk
     }
@@ -423,3 +460,31 @@ __global__ __launch_bounds__(64, MINW) void k_inflate2(rcx_kargs a, int zlib)
     if (a.in_used) a.in_used[b] = used;
     if (a.aux) a.aux[b] = flags;
 }
+
+// Streams per wave for n streams: the largest of 32/16/8 that still gives 2048 waves (measured: benchmarks/inflate_spw_sweep.py;
+// full waves are never the fastest).  F2_LAUNCH: kernel K<spw, log2 spw, 1> over k.nblocks streams, spw lanes a workgroup.
+static int f2_streams_per_wave(uint32_t n) { return n >= 32u * 2048u ? 32 : n >= 16u * 2048u ? 16 : 8; }
+#define F2_LAUNCH(K, spw, s, k, z)                                                                                       \
+    do {                                                                                                                  \
+        const uint32_t n_ = (k).nblocks;                                                                                  \
+        if ((spw) >= 32) hipLaunchKernelGGL((K<32, 5, 1>), dim3((n_ + 31) / 32), dim3(32), 0, s, k, z);                   \
+        else if ((spw) == 16) hipLaunchKernelGGL((K<16, 4, 1>), dim3((n_ + 15) / 16), dim3(16), 0, s, k, z);              \
+        else hipLaunchKernelGGL((K<8, 3, 1>), dim3((n_ + 7) / 8), dim3(8), 0, s, k, z);                                   \
+    } while (0)
+
+// one lane per stream (k_inflate2); `flags`: bit 0 zlib framing, bit 1 only the blocks k_inflate3 handed back; variants 2..8 pin
+// the geometry (A/B)
+static void launch_inflate2(hipStream_t s, rcx_kargs& k, int flags, int v)
+{
+    const uint32_t n = k.nblocks;
+    const int spw = v == 2 ? 64 : v == 3 ? 32 : v == 4 ? 16 : v == 5 ? 8 : f2_streams_per_wave(n);
+    const int z = flags;
+#ifdef RCX_AB_VARIANTS
+    if (v == 6) { hipLaunchKernelGGL((k_inflate2<16, 4, 4>), dim3((n + 15) / 16), dim3(16), 0, s, k, z); return; }
+    if (v == 7) { hipLaunchKernelGGL((k_inflate2<32, 5, 3>), dim3((n + 31) / 32), dim3(32), 0, s, k, z); return; }
+    if (v == 8) { hipLaunchKernelGGL((k_inflate2<16, 4, 3>), dim3((n + 15) / 16), dim3(16), 0, s, k, z); return; }
+    if (spw == 64) { hipLaunchKernelGGL((k_inflate2<64, 6, 1>), dim3((n + 63) / 64), dim3(64), 0, s, k, z); return; }
+#endif
+    F2_LAUNCH(k_inflate2, spw, s, k, z);
+}
+

@@ -1,21 +1,23 @@
 // k_inflate_hist.hip -- DEFLATE / zlib decode with HISTORY: stream b's matches may reach into the hist[b] bytes (at most 32768) that
 // lie directly before its slot in the output buffer -- a preset dictionary (RFC 1950 FDICT, zlib's inflateSetDictionary), or the 32 KiB
 // in front of a chunk of one long stream.  The mirror of dict_len in k_lz4_linked.hip.  Included behind k_inflate2.hip: one LANE per
-// stream on that file's F2 machinery (tables, bit reader, ring, f2_codes / f2_stored / f2_fixed / f2_dynamic), unchanged.
+// stream on that file's F2 machinery (tables, bit reader, ring, f2_stored / f2_fixed / f2_dynamic with the slot source policy).
 //
 // NOT in the reference crate (src/zlib.rs:71 refuses FDICT): an extension, checked against libz (zdict=).
 //
 // The stream is decoded as a VIRTUAL stream that starts hist bytes behind its slot: F2::out points at the first history byte, end and
-// flushed start at hist, cap grows by hist.  f2_codes' window rule (flate.rs:314: distance <= min(output so far, 32768)) then counts the
-// history in, far matches gather from out + (end - distance) whether that lies in the history or in the slot, and the drain stores
-// [flushed, end) only: the history is read and never written.  omis and the 16-byte drains follow the virtual pointer.  Distances
-// below F2_NEAR are served from the 128-byte ring, so the ring is seeded with the last min(hist, 128) history bytes -- not through
-// emit: the Adler-32 sums (the zlib trailer covers the decoded block alone) must not see them.
+// flushed start at hist, cap grows by hist.  The slot source policy's window rule (flate.rs:314: distance <= min(output so far, 32768))
+// then counts the history in, far matches gather from out + (end - distance) whether that lies in the history or in the slot, and the
+// drain stores [flushed, end) only: the history is read and never written; out_len is end - hist.  omis and the 16-byte drains follow
+// the virtual pointer.  Distances below F2_NEAR are served from the 128-byte ring, so the ring is seeded with the last
+// min(hist, 128) history bytes -- not through emit: the Adler-32 sums (the zlib trailer covers the decoded block alone) must not see
+// them.
 //
 // aux[b] = hist[b] (uint32) when the kernel starts, the stream's flags when it ends; zlib form: aux[n + b] = the DICTID the caller
 // expects.  zlib header (RFC 1950 2.2): FDICT clear -- the history is ignored (libz never asks for one) and the stream is
-// k_inflate2's; FDICT set and no history -- RCX_E_ZLIB_DICT as there; FDICT set and a history -- the four DICTID bytes behind the
-// header count in in_used and must equal aux[n + b], else RCX_E_ZLIB_DICT_ID with nothing decoded.
+// k_inflate2's; FDICT set and no history -- RCX_E_ZLIB_DICT as there (checked before the header checksum); FDICT set and a history
+// -- the four DICTID bytes behind the header count in in_used and must equal aux[n + b], else RCX_E_ZLIB_DICT_ID with nothing
+// decoded; a stream that ends inside them is RCX_E_EOF with every byte used.
 
 template <int SPW, int LG, int MINW>
 __global__ __launch_bounds__(64, MINW) void k_inflate_hist(rcx_kargs a, int zlib)
@@ -67,8 +69,8 @@ __global__ __launch_bounds__(64, MINW) void k_inflate_hist(rcx_kargs a, int zlib
         if (x == 1) eof = true;                                            // :198
         if ((st = s.bits(2, x))) break;                                    // :199
         if (x == 0) st = f2_stored(s);
-        else if (x == 1) st = f2_fixed(s, HL, HD, lens);
-        else if (x == 2) st = f2_dynamic(s, HL, HD, lens);
+        else if (x == 1) st = f2_fixed(s, HL, HD, lens, F2SlotSrc{});
+        else if (x == 2) st = f2_dynamic(s, HL, HD, lens, F2SlotSrc{});
         else st = RCX_E_INVALID_BLOCK_CODE;                                // :203
         if (!st && s.end == before && !eof) flags |= RCX_W_EMPTY_BLOCK_MIDSTREAM;   // :474-476 quirk
     }
@@ -91,12 +93,8 @@ __global__ __launch_bounds__(64, MINW) void k_inflate_hist(rcx_kargs a, int zlib
     a.aux[b] = flags;
 }
 
-// k.aux: n history lengths (+ n DICTIDs: zlib), never null.  Streams per wave as launch_inflate2 chooses them.
+// k.aux: n history lengths (+ n DICTIDs: zlib), never null
 static void launch_inflate_hist(hipStream_t s, rcx_kargs& k, bool zlib)
 {
-    const uint32_t n = k.nblocks;
-    const int z = zlib ? 1 : 0;
-    if (n >= 32u * 2048u) hipLaunchKernelGGL((k_inflate_hist<32, 5, 1>), dim3((n + 31) / 32), dim3(32), 0, s, k, z);
-    else if (n >= 16u * 2048u) hipLaunchKernelGGL((k_inflate_hist<16, 4, 1>), dim3((n + 15) / 16), dim3(16), 0, s, k, z);
-    else hipLaunchKernelGGL((k_inflate_hist<8, 3, 1>), dim3((n + 7) / 8), dim3(8), 0, s, k, z);
+    F2_LAUNCH(k_inflate_hist, f2_streams_per_wave(k.nblocks), s, k, zlib ? 1 : 0);
 }

@@ -208,6 +208,21 @@ def lz_apply(hist, tokens):
     return bytes(buf[len(hist):])
 
 
+F2_NEAR = 112                                  # k_inflate2.hip: distances from here on are gathered from memory, not read from the ring
+
+
+def far_gathers(tokens):
+    """the slot positions at which the lane-per-stream decoder gathers 16 bytes of a far source: one gather per 16 bytes of a match
+    at a distance >= F2_NEAR, the first at (the match's start - distance).  A negative position lies behind the slot's first byte
+    (in the history or dictionary); one in -15 .. -1 is a gather that straddles position 0."""
+    pos, at = 0, []
+    for ln, x in tokens:
+        if ln and x >= F2_NEAR:
+            at += [pos - x + k for k in range(0, ln, 16)]
+        pos += ln or 1
+    return at
+
+
 def libz_raw(hist, tokens_stream):
     """libz's answer to a raw stream behind `hist`: the bytes, or None (an error)"""
     d = zlib.decompressobj(-15, zdict=hist) if hist else zlib.decompressobj(-15)
@@ -228,6 +243,12 @@ MODES = (0, 1, 6, 9, "fixed")
 _dec = None
 
 
+def first_match_tokens(d):
+    """the first symbol a match of 258 bytes at distance d (all of its source behind position 0, or running over it), then a literal
+    and a short match"""
+    return [(258, d), (0, 65), (7, 2)]
+
+
 def decode_cases():
     """[dict(name, stream, hist, cap, front, want (bytes or None), status)] of raw DEFLATE streams"""
     global _dec
@@ -244,10 +265,11 @@ def decode_cases():
                 continue
             add("libz %s h%d n%d" % (m, len(h), len(b)), libz_stream(h, b, m), h, b)
     # hand-assembled: the first symbol a match of 258 bytes at a distance on both sides of F2_NEAR (112), from the history into the
-    # stream (overlapping where the distance is short)
+    # stream (overlapping where the distance is short: 1, 2 and 3 repeat inside one 4-byte step and read the seeded ring alone); at
+    # 113 a 16-byte gather of the source straddles the first byte of the slot
     hist = rand(300, 11)
-    for d in (1, 2, 111, 112, 113, 300):
-        toks = [(258, d), (0, 65), (7, 2)]
+    for d in (1, 2, 3, 111, 112, 113, 300):
+        toks = first_match_tokens(d)
         add("first match d%d" % d, fixed_stream(toks), hist, lz_apply(hist, toks))
     # the reach: output so far + history, exactly; one more is an error
     hist = rand(100, 12)

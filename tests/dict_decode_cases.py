@@ -205,7 +205,7 @@ def hand(family):
             """the first symbol a match of ML bytes at distance d, then a literal and a short match"""
             if lz4:
                 return corpus.lz4_stream([(b"", ML, d), (b"A", 7, 2)], b"tail!"), lz_apply(D, [(b"", ML, d), (b"A", 7, 2)], b"tail!")
-            toks = [(ML, d), (0, 65), (7, 2)]
+            toks = DH.first_match_tokens(d)
             return DH.fixed_stream(toks), DH.lz_apply(D, toks)
         # the dictionary's end at every residue mod 16 of the buffer (the far gather splits there), the split at every byte of a gather
         for r in range(16):
@@ -256,12 +256,15 @@ def hand(family):
 
 
 def zlib_cases():
-    """the seven zlib_decode_cases() (FDICT, DICTID, the trailer over the block alone), each stream behind the dictionary it is told"""
+    """the seven zlib_decode_cases() (FDICT, DICTID, the trailer over the block alone), each stream behind the dictionary it is told;
+    the last one's dictionary, which its stream does use, ends at the buffer's last byte"""
     def make():
         B = DBatch("zlib")
-        for k, c in enumerate(DH.zlib_decode_cases()):
+        cs = DH.zlib_decode_cases()
+        for k, c in enumerate(cs):
             D = c["hist"][len(c["hist"]) - c["told"]:] if c["told"] else b""
-            d = B.dict(D, front=b"\xC3" * (1 + k % 3), after=bool(k & 1)) if D else None
+            last = k == len(cs) - 1
+            d = B.dict(D, front=b"\xC3" * (1 + k % 3), behind=b"" if last else b"\x3C\x3C", after=last or bool(k & 1)) if D else None
             B.rec(c["name"], c["stream"], d, len(c["want"]) if c["status"] in (0, DH.E_ZLIB_CHECKSUM) else 16, did=c["dict_id"],
                   want=(c["status"], c["want"] if c["status"] == 0 else None))
         return B

@@ -263,6 +263,10 @@ def test_decode_cases_are_what_they_say():
             got = K.libz_raw(c["hist"], c["stream"])
             assert got == (c["want"] if c["status"] == 0 else None), name
     assert cs["d32768 h32768 p1"]["status"] == 0 and cs["d32768 h32767 p0"]["status"] == K.E_INVALID_HUFFMAN_CODE
+    # distances 1, 2 and 3 at output position 0 (the seeded ring alone), and a far gather that straddles the slot's first byte (the
+    # other fourteen splits: the "end residue" cases of dict_decode_cases.py, which test_wavesim_dict_decode.py runs through this kernel)
+    assert all(cs["first match d%d" % d]["status"] == 0 and len(cs["first match d%d" % d]["hist"]) >= d for d in (1, 2, 3))
+    assert -1 in K.far_gathers(K.first_match_tokens(113)) and cs["first match d113"]["status"] == 0
 
 
 def test_decode(decoded):

@@ -60,6 +60,28 @@ def test_the_cases_cover_what_they_claim(family):
     # the bait pair: equal outputs, equal to the reference
     x, y = hand.index("end bait x"), hand.index("end bait y")
     assert h["outputs"][x] == h["outputs"][y] == hand.want[x][1] and int(h["status"][x]) == 0
+    # distances 1, 2 and 3 at output position 0: nothing but the seeded ring to read
+    assert all(st["first match d%d" % d] == 0 and hand.want[hand.index("first match d%d" % d)][1] for d in (1, 2, 3))
+    if family == "deflate":
+        import deflate_hist_cases as DH
+        # a 16-byte gather of a far source that straddles position 0, split after every count of dictionary bytes; both kernels take
+        # it: _both() sends the batch through k_inflate_dict and, on the replicated layout, through k_inflate_hist
+        splits = {-s for r in range(16) for s in DH.far_gathers(DH.first_match_tokens(112 + r)) if -16 < s < 0}
+        assert splits == set(range(1, 16)) and all(st["end residue %d" % r] == 0 for r in range(16))
+        # ... and whole gathers on both sides of it: from the dictionary alone (the first of every far match here), from the slot alone.
+        # (A far source ends 96 bytes or more below the output's end, inside the slot: no case can make its gather pass the slot's
+        # capacity, so the byte-wise tail of the slot policy has none.)
+        at = DH.far_gathers(DH.first_match_tokens(112))
+        assert at[0] == -112 and 0 in at
+        # zlib: FDICT with a wrong DICTID and FDICT with no dictionary; a dictionary in use that ends at the buffer's last byte
+        zl = DC.zlib_cases()
+        (z, _), = _both([zl])
+        zst = {nm: int(s) for nm, s in zip(zl.names, z["status"])}
+        assert zst["wrong id"] == DH.E_ZLIB_DICT_ID and zst["fdict, no history"] == DH.E_ZLIB_DICT
+        buf, _, _, d_off, d_len = zl.layout()
+        i = zl.index("short history")
+        assert d_off[i] + d_len[i] == buf.size and zst["short history"] == 0 and z["outputs"][i] == zl.want[i][1]
+        assert DH.libz_raw(b"", zl.blocks[i][6:-4]) is None               # (without the dictionary libz cannot read it)
 
 
 def test_zlib_cases_carry_their_statuses():
