@@ -6,13 +6,18 @@
 // parity of the round that made the group.  Round 0 sorts by a 64-bit key of the first <= 10 symbols, round r > 0 by the 32-bit
 // key `rank[suffix + h]` (0 = past the end: the reference's "a proper prefix sorts first"), gathered for every non-final
 // position before anything is moved.  A group is then sorted by the path that fits its size:
-//   * more than 64 suffixes: k_bws_partition, one workgroup per group: MSD radix step on 8 key bits (per-wave histograms in
-//     LDS, scatter to the other buffer); bins of more than 64 are groups of the next level, singletons are final at once,
-//     everything in between is marked in place for the wave-level sorts;
-//   * at most 64, inside a 64-suffix window (aligned, or shifted by 32) -- nearly all groups of a text: k_bws_dense, ONE LANE
-//     PER SUFFIX over the whole array: the HEAD bits of a window give every lane its group, a wave-wide bitonic sort over
-//     ds_bpermute by (group, key) orders every group of the window at once.  No descriptors, no launch per group;
-//   * the few groups of 33..64 that straddle both window grids: k_bws_small, one wave per group, the same wave sort.
+//   * more than BWS_LMAX (2048) suffixes: k_bws_partition, one workgroup per group: MSD radix step on 8 key bits (per-wave
+//     histograms in LDS, scatter to the other buffer); bins of more than BWS_LMAX are groups of the next level, singletons are
+//     final at once, bins of at most BWS_WAVE are marked in place for the dense passes, the bins in between go to the LDS sorts;
+//   * BWS_WAVE+1 .. BWS_LWAVE (33..256) and BWS_LWAVE+1 .. BWS_LMAX (257..2048) suffixes: k_bws_local_wave and k_bws_local_wg,
+//     one wave or one workgroup per group: sorted to the end of the key inside LDS (LSD radix passes over a permutation);
+//   * at most BWS_WAVE (32), inside a 64-suffix window (aligned, or shifted by 32) -- nearly all groups of a text: k_bws_dense,
+//     ONE LANE PER SUFFIX over the whole array: the HEAD bits of a window give every lane its group; a rank sort over
+//     ds_bpermute when the window's largest group has at most 12 suffixes, else a wave-wide bitonic sort by (group, key)
+//     orders every group of the window at once.  No descriptors, no launch per group;
+//   * k_bws_small (one wave per group, the same wave sort) takes the groups of at most BWS_WAVE that lie in neither window grid.
+//     With BWS_WAVE = 32 there are none: 32 consecutive positions that cross a multiple of 64 lie inside the window shifted by
+//     32, so bws_dense_ok holds for every such group and the kernel's list stays empty.  It is kept for a larger BWS_WAVE.
 // Every path ends the same way: runs of equal keys are the new groups (rank = position of the run's first suffix, written in
 // place -- the keys of the round were gathered before), runs of one are FINAL.  Groups that the dense pass cannot take are
 // appended to the next round's lists.  Per suffix and round: one gather of a rank (random), one scatter of a rank (random) and
@@ -791,7 +796,7 @@ __global__ void k_bws_round_end(BwsState s)
     for (uint32_t f = t; f < BWS_NFLAG; f += blockDim.x) s.cnt[64u + f] = 0u;
 }
 
-// ---- the few groups of <= 64 the dense passes cannot take (33..64 suffixes across both window grids): one wave per group ----
+// ---- groups of <= BWS_WAVE the dense passes cannot take, one wave per group (none with BWS_WAVE = 32: see the header) ----------
 template <class K>
 __global__ __launch_bounds__(256) RCX_SGPR_CAP void k_bws_small(BwsState s, uint32_t top_shift)
 {
@@ -818,7 +823,7 @@ __global__ __launch_bounds__(256) RCX_SGPR_CAP void k_bws_small(BwsState s, uint
     }
 }
 
-// ---- groups of <= 64 inside a window: one lane per suffix over the whole array ----------------------------------------------
+// ---- groups of <= BWS_WAVE (32) inside a 64-suffix window: one lane per suffix over the whole array -------------------------
 // Windows of 64 suffixes starting at `off` (0 or 32: a group of <= 32 suffixes that straddles an aligned window lies inside a
 // shifted one).  The lanes of a window sort by (start of my group, key, lane): that orders every group the window contains
 // and moves nothing else -- a wave-wide bitonic sort over ds_bpermute (21 compare-exchange steps whatever the group sizes).
