@@ -1223,6 +1223,10 @@ __global__ __launch_bounds__(128, 8) void k_lz4_decode_v8(rcx_kargs a, int only_
     __shared__ __align__(16) uint8_t s_cbuf[S::CBUF8 + 16];
     __shared__ int16_t s_list[S::LISTN];
     __shared__ uint32_t s_lmap[64];
+    // sixteen workgroups a CU (eight waves a SIMD) need <= 10240 bytes each: the shipped instantiation stands at 10192 with rows of twelve dwords
+    static_assert(!(X6 && TC == 1024 && HH == 768 && !PROF8 && RCX_X6_MODE == 1) ||
+                  ((sizeof(s_mtab) + 15) & ~15u) + ((sizeof(s_wbuf) + 15) & ~15u) + ((sizeof(s_ring) + 15) & ~15u) + ((sizeof(s_cbuf) + 15) & ~15u) +
+                  ((sizeof(s_list) + 15) & ~15u) + sizeof(s_lmap) <= 10240, "k_lz4_decode_v8: more LDS than sixteen workgroups a CU allow");
     const uint32_t b = blockIdx.x;
     if (b >= a.nblocks) return;
     if (only_status && a.status[b] != only_status) return;

@@ -13,7 +13,22 @@
 // (Lz4V5 / Lz4V4 -- k_lz4_decode_v5.hip, k_lz4_decode_v4.hip -- come first in the translation unit: tu_lz4.hip)
 
 #ifndef RCX_X6_MROW
-#define RCX_X6_MROW 9                        /* dwords a row of the mask table (8: rows 32 bytes apart, read as b128 + b32 -- the k-th dwords of rows e, e + 4, e + 8 ... share a bank) */
+#define RCX_X6_MROW 12                       /* dwords a row of the mask table.  A multiple of 4: rows 16-byte aligned, read as ds_read_b128 + ds_read_b32 (6 LDS cycles;
+                                               dword by dword, as hipcc pairs them: read2 + read2 + read, 10).  12: the 20 rows' quads on 20 different quads of the 64 banks,
+                                               the fifth dwords of rows 8 apart in one bank; 8: the k-th dwords of rows e, e + 4, e + 8 ... share a bank; 9 (the
+                                               table until now, 720 bytes): no two rows' k-th dwords in one bank, no wide read */
+#endif
+#define RCX_X6_MROW_WIDE ((RCX_X6_MROW) % 4 == 0)
+#ifndef RCX_X6_NW4
+#define RCX_X6_NW4 3                        /* a frame store whose lanes all end within the frame's first four dwords (a + n <= 16: one compare, one wave-uniform branch)
+                                               issues four atomics, not five: bit 0 = in the hand-written copy rounds, bit 1 = in emit6's compiled stores, 0 = always five
+                                               (A/B).  fill_run and emit5 keep five.  44 % of a text's frame stores (tests/test_wavesim_lz4_frames.py).  As two copies of
+                                               the store, one of four and one of five atomics, the compiled stores spilled four VGPRs: it is ONE store with a scalar
+                                               branch around its fifth atomic. */
+#endif
+#ifndef RCX_X6_PAIR
+#define RCX_X6_PAIR 1                       /* the hand-written copy rounds read their six source dwords as three ds_read2_b32 (and a row of a table that has no wide
+                                               read as read2 + read2 + read); 0 = dword by dword (A/B).  hipcc pairs the reads of the compiled paths by itself. */
 #endif
 #ifndef RCX_X6_RR
 #define RCX_X6_RR 3                         /* emit6's redirection rounds (pointer doubling) before the copy rounds: 0 / 1 / 2 / 3 / 4 / 5 / 6: 0.587 / 0.485 / 0.4516 / 0.4468 /
@@ -34,19 +49,66 @@
 #ifndef RCX_V8_STAT
 #define RCX_V8_STAT(slot, v) ((void)0)                       /* the wave simulator counts batches through emit6 / emit5 here */
 #endif
+#ifdef RCX_X6_FRAME_STATS                   /* simulator builds of tests/test_wavesim_lz4_frames.py (the simulator's 32 slots are all taken): [0] frame stores of emit6 --
+                                               one for the whole wave -- outside fill_run, [1] those of them in which no lane reaches the fifth dword, [2] gathered matches (entries) */
+inline unsigned long long g_x6_frame_stat[4];
+extern "C" __attribute__((used, visibility("default"))) inline unsigned long long* rcx_x6_frame_stats() { return g_x6_frame_stat; }
+#define RCX_X6_STAT(slot, v) (g_x6_frame_stat[slot] += (unsigned long long)(v))
+#else
+#define RCX_X6_STAT(slot, v) ((void)0)
+#endif
 
 // The copy rounds of Lz4V8::emit6 as ISA (the loop of rcx_lz4_rounds, k_lz4_decode_v5.hip, with emit6's store): every round the lanes whose
 // producers are done -- no pending lane among `dep` -- read six aligned dwords from `source - a` (a: the destination's misalignment), shift them
-// by the source's own and store up to 16 bytes as five ds_mskor_b32 under the masks of table entry a + n.  exec holds the ready lanes only: an LDS
-// atomic under an empty mask would still take its turn at the dwords it shares with its neighbours.  24 vector + 4 scalar instructions a round
-// (hipcc's loop for the same source: 44 + 6, every lane at every LDS instruction).
+// by the source's own and store up to 16 bytes as four or five ds_mskor_b32 under the masks of table entry a + n.  exec holds the ready lanes
+// only: an LDS atomic under an empty mask would still take its turn at the dwords it shares with its neighbours.  24 vector ALU instructions a
+// round, 25 with the test of the fifth masks (hipcc's loop for the same source: 44 + 6 scalar, every lane at every LDS instruction).
 //   s0: LDS address of source - a; d4: LDS address of the destination's frame (4-byte aligned); mc: bytes to copy (0: none); tb: LDS address of
-//   the mask table + 32 a; fix: ~0 << 8 a.  Returns the lanes still pending when no lane is ready: none, unless a lane was handed a dependency on
+//   the mask table + a rows; fix: ~0 << 8 a.  Returns the lanes still pending when no lane is ready: none, unless a lane was handed a dependency on
 //   itself (emit6 does that to a run, which it fills itself).
+// ONE loop for every value of the switches.  A ds_read2_b32 / ds_read_b128 returns into an aligned register pair / quad whose dwords the
+// shifts and the stores name one by one, and an asm operand has no name for a half of itself: the six source dwords and the row's first
+// four masks live in v[48:53] and v[44:47], named here and declared clobbered.  All reads of a round are in flight at once; the waits count
+// them back in issue order (LDS operations return in order, the atomics count as well):
+//   pairs + wide row   S01 S23 S45 M M4        4 / 3 / 2 for the shifts, 1 for the first mask, 4 -- M4 and four atomics in front -- for the fifth
+//   pairs + read2 row  S01 S23 S45 M01 M23 M4  5 / 4 / 3, 2, then 3 (M23 M4 + two atomics) for the third mask, 4 for the fifth
+//   dwords + wide row  S0 .. S5 M M4           6 / 5 / 4 / 3 / 2, 1, 4
+//   dwords + dword row S0 .. S5 M0 .. M4       9 / 8 / 7 / 6 / 5, then 4 in front of every mask (the loop as it was before the switches)
+// LDS instructions of a round at pairs + wide row: 5 reads + 4 or 5 atomics behind 6 waits (dword by dword: 11 + 5 behind 10).
+// RCX_X6_NW4: the fifth mask is zero in every lane that stores unless one of them ends beyond the frame's first 16 bytes; then the fifth atomic
+// is skipped (the wait in front of it stays: no read is left in flight when the loop is done with its registers).
 #if !defined(RCX_NO_ROUNDS_ASM) && !defined(RCX_NO_MSKOR_ASM)
+// (the named registers: below the kernel's 64-VGPR budget, contiguous, the quad's first register a multiple of 4 and each pair's even)
+#define RCX_R6_S0 "v48"
+#define RCX_R6_S1 "v49"
+#define RCX_R6_S2 "v50"
+#define RCX_R6_S3 "v51"
+#define RCX_R6_S4 "v52"
+#define RCX_R6_S5 "v53"
+#define RCX_R6_M0 "v44"
+#define RCX_R6_M1 "v45"
+#define RCX_R6_M2 "v46"
+#define RCX_R6_M3 "v47"
+#if RCX_X6_PAIR
+#define RCX_R6_SRC_READS "ds_read2_b32 v[48:49], %[t0] offset1:1\n\tds_read2_b32 v[50:51], %[t0] offset0:2 offset1:3\n\tds_read2_b32 v[52:53], %[t0] offset0:4 offset1:5\n\t"
+#define RCX_R6_NSRC 3
+#else
+#define RCX_R6_SRC_READS "ds_read_b32 v48, %[t0]\n\tds_read_b32 v49, %[t0] offset:4\n\tds_read_b32 v50, %[t0] offset:8\n\tds_read_b32 v51, %[t0] offset:12\n\tds_read_b32 v52, %[t0] offset:16\n\tds_read_b32 v53, %[t0] offset:20\n\t"
+#define RCX_R6_NSRC 6
+#endif
+#if RCX_X6_MROW_WIDE
+#define RCX_R6_ROW_READS "ds_read_b128 v[44:47], %[t1]\n\tds_read_b32 %[m4], %[t1] offset:16\n\t"
+#define RCX_R6_NROW 2
+#elif RCX_X6_PAIR
+#define RCX_R6_ROW_READS "ds_read2_b32 v[44:45], %[t1] offset1:1\n\tds_read2_b32 v[46:47], %[t1] offset0:2 offset1:3\n\tds_read_b32 %[m4], %[t1] offset:16\n\t"
+#define RCX_R6_NROW 3
+#else
+#define RCX_R6_ROW_READS "ds_read_b32 v44, %[t1]\n\tds_read_b32 v45, %[t1] offset:4\n\tds_read_b32 v46, %[t1] offset:8\n\tds_read_b32 v47, %[t1] offset:12\n\tds_read_b32 %[m4], %[t1] offset:16\n\t"
+#define RCX_R6_NROW 5
+#endif
 __device__ __forceinline__ uint64_t rcx_lz4_rounds6(uint32_t s0, uint32_t d4, uint32_t mc, uint32_t dep_lo, uint32_t dep_hi, uint64_t pend, uint32_t tb, uint32_t fix)
 {
-    uint32_t t0, t1, nv, sa, sh, da, r0, r1, r2, r3, r4, r5, m0, m1, m2, m3, m4, prog = 0;
+    uint32_t t0, t1, nv, sa, sh, da, m4, prog = 0;
     uint64_t sT, sF;
     asm volatile(
         "s_mov_b64 vcc, %[pend]\n\t"
@@ -60,49 +122,63 @@ __device__ __forceinline__ uint64_t rcx_lz4_rounds6(uint32_t s0, uint32_t d4, ui
         "v_add_u32_e32 %[sa], %[s0], %[prog]\n\t"
         "v_sub_u32_e32 %[nv], %[mc], %[prog]\n\t"
         "v_and_b32_e32 %[t0], -4, %[sa]\n\t"
-        "ds_read_b32 %[r0], %[t0]\n\t"
-        "ds_read_b32 %[r1], %[t0] offset:4\n\t"
-        "ds_read_b32 %[r2], %[t0] offset:8\n\t"
-        "ds_read_b32 %[r3], %[t0] offset:12\n\t"
-        "ds_read_b32 %[r4], %[t0] offset:16\n\t"
-        "ds_read_b32 %[r5], %[t0] offset:20\n\t"
+        RCX_R6_SRC_READS
         "v_min_u32_e32 %[nv], 16, %[nv]\n\t"
         "v_mad_u32_u24 %[t1], %[nv], %[mrow], %[tb]\n\t"
-        "ds_read_b32 %[m0], %[t1]\n\t"
-        "ds_read_b32 %[m1], %[t1] offset:4\n\t"
-        "ds_read_b32 %[m2], %[t1] offset:8\n\t"
-        "ds_read_b32 %[m3], %[t1] offset:12\n\t"
-        "ds_read_b32 %[m4], %[t1] offset:16\n\t"
+        RCX_R6_ROW_READS
         "v_and_b32_e32 %[sh], 3, %[sa]\n\t"
         "v_add_u32_e32 %[da], %[d4], %[prog]\n\t"
         "v_add_u32_e32 %[prog], %[prog], %[nv]\n\t"
         "v_cmp_ge_u32_e64 %[sF], %[prog], %[mc]\n\t"              // of this round's lanes, those that are done with it
-        "s_waitcnt lgkmcnt(9)\n\t"
-        "v_alignbyte_b32 %[r0], %[r1], %[r0], %[sh]\n\t"
-        "s_waitcnt lgkmcnt(8)\n\t"
-        "v_alignbyte_b32 %[r1], %[r2], %[r1], %[sh]\n\t"
-        "s_waitcnt lgkmcnt(7)\n\t"
-        "v_alignbyte_b32 %[r2], %[r3], %[r2], %[sh]\n\t"
-        "s_waitcnt lgkmcnt(6)\n\t"
-        "v_alignbyte_b32 %[r3], %[r4], %[r3], %[sh]\n\t"
-        "s_waitcnt lgkmcnt(5)\n\t"
-        "v_alignbyte_b32 %[r4], %[r5], %[r4], %[sh]\n\t"
+#if RCX_X6_PAIR
+        "s_waitcnt lgkmcnt(%c[w0])\n\t"
+        "v_alignbyte_b32 " RCX_R6_S0 ", " RCX_R6_S1 ", " RCX_R6_S0 ", %[sh]\n\t"
+        "s_waitcnt lgkmcnt(%c[w1])\n\t"
+        "v_alignbyte_b32 " RCX_R6_S1 ", " RCX_R6_S2 ", " RCX_R6_S1 ", %[sh]\n\t"
+        "v_alignbyte_b32 " RCX_R6_S2 ", " RCX_R6_S3 ", " RCX_R6_S2 ", %[sh]\n\t"
+        "s_waitcnt lgkmcnt(%c[w2])\n\t"
+        "v_alignbyte_b32 " RCX_R6_S3 ", " RCX_R6_S4 ", " RCX_R6_S3 ", %[sh]\n\t"
+        "v_alignbyte_b32 " RCX_R6_S4 ", " RCX_R6_S5 ", " RCX_R6_S4 ", %[sh]\n\t"
+#else
+        "s_waitcnt lgkmcnt(%c[w0])\n\t"
+        "v_alignbyte_b32 " RCX_R6_S0 ", " RCX_R6_S1 ", " RCX_R6_S0 ", %[sh]\n\t"
+        "s_waitcnt lgkmcnt(%c[w0b])\n\t"
+        "v_alignbyte_b32 " RCX_R6_S1 ", " RCX_R6_S2 ", " RCX_R6_S1 ", %[sh]\n\t"
+        "s_waitcnt lgkmcnt(%c[w0c])\n\t"
+        "v_alignbyte_b32 " RCX_R6_S2 ", " RCX_R6_S3 ", " RCX_R6_S2 ", %[sh]\n\t"
+        "s_waitcnt lgkmcnt(%c[w0d])\n\t"
+        "v_alignbyte_b32 " RCX_R6_S3 ", " RCX_R6_S4 ", " RCX_R6_S3 ", %[sh]\n\t"
+        "s_waitcnt lgkmcnt(%c[w0e])\n\t"
+        "v_alignbyte_b32 " RCX_R6_S4 ", " RCX_R6_S5 ", " RCX_R6_S4 ", %[sh]\n\t"
+#endif
+        "s_waitcnt lgkmcnt(%c[wm])\n\t"                            // the row's first read: its first mask (wide: its first four)
+        "v_and_b32_e32 " RCX_R6_M0 ", " RCX_R6_M0 ", %[fix]\n\t"
+        "v_and_b32_e32 " RCX_R6_S0 ", " RCX_R6_S0 ", " RCX_R6_M0 "\n\t"
+        "ds_mskor_b32 %[da], " RCX_R6_M0 ", " RCX_R6_S0 "\n\t"
+#if !RCX_X6_MROW_WIDE && !RCX_X6_PAIR
         "s_waitcnt lgkmcnt(4)\n\t"
-        "v_and_b32_e32 %[m0], %[m0], %[fix]\n\t"
-        "v_and_b32_e32 %[r0], %[r0], %[m0]\n\t"
-        "ds_mskor_b32 %[da], %[m0], %[r0]\n\t"
+#endif
+        "v_and_b32_e32 " RCX_R6_S1 ", " RCX_R6_S1 ", " RCX_R6_M1 "\n\t"
+        "ds_mskor_b32 %[da], " RCX_R6_M1 ", " RCX_R6_S1 " offset:4\n\t"
+#if !RCX_X6_MROW_WIDE
+        "s_waitcnt lgkmcnt(%c[wm2])\n\t"
+#endif
+        "v_and_b32_e32 " RCX_R6_S2 ", " RCX_R6_S2 ", " RCX_R6_M2 "\n\t"
+        "ds_mskor_b32 %[da], " RCX_R6_M2 ", " RCX_R6_S2 " offset:8\n\t"
+#if !RCX_X6_MROW_WIDE && !RCX_X6_PAIR
         "s_waitcnt lgkmcnt(4)\n\t"
-        "v_and_b32_e32 %[r1], %[r1], %[m1]\n\t"
-        "ds_mskor_b32 %[da], %[m1], %[r1] offset:4\n\t"
-        "s_waitcnt lgkmcnt(4)\n\t"
-        "v_and_b32_e32 %[r2], %[r2], %[m2]\n\t"
-        "ds_mskor_b32 %[da], %[m2], %[r2] offset:8\n\t"
-        "s_waitcnt lgkmcnt(4)\n\t"
-        "v_and_b32_e32 %[r3], %[r3], %[m3]\n\t"
-        "ds_mskor_b32 %[da], %[m3], %[r3] offset:12\n\t"
-        "s_waitcnt lgkmcnt(4)\n\t"
-        "v_and_b32_e32 %[r4], %[r4], %[m4]\n\t"
-        "ds_mskor_b32 %[da], %[m4], %[r4] offset:16\n\t"
+#endif
+        "v_and_b32_e32 " RCX_R6_S3 ", " RCX_R6_S3 ", " RCX_R6_M3 "\n\t"
+        "ds_mskor_b32 %[da], " RCX_R6_M3 ", " RCX_R6_S3 " offset:12\n\t"
+        "s_waitcnt lgkmcnt(4)\n\t"                                 // the fifth mask: four atomics behind it
+#if RCX_X6_NW4 & 1
+        "v_cmp_ne_u32_e64 %[sT], 0, %[m4]\n\t"
+        "s_cmp_eq_u64 %[sT], 0\n\t"
+        "s_cbranch_scc1 L_four_%=\n\t"
+#endif
+        "v_and_b32_e32 " RCX_R6_S4 ", " RCX_R6_S4 ", %[m4]\n\t"
+        "ds_mskor_b32 %[da], %[m4], " RCX_R6_S4 " offset:16\n\t"
+        "L_four_%=:\n\t"
         "s_mov_b64 exec, -1\n\t"
         "s_andn2_b64 vcc, vcc, %[sF]\n\t"                          // scc: a lane still pending
         "s_cbranch_scc1 L_top_%=\n\t"
@@ -110,10 +186,12 @@ __device__ __forceinline__ uint64_t rcx_lz4_rounds6(uint32_t s0, uint32_t d4, ui
         "s_mov_b64 exec, -1\n\t"
         "s_mov_b64 %[pend], vcc\n\t"
         : [pend] "+s"(pend), [prog] "+v"(prog), [t0] "=&v"(t0), [t1] "=&v"(t1), [nv] "=&v"(nv), [sa] "=&v"(sa), [sh] "=&v"(sh), [da] "=&v"(da),
-          [r0] "=&v"(r0), [r1] "=&v"(r1), [r2] "=&v"(r2), [r3] "=&v"(r3), [r4] "=&v"(r4), [r5] "=&v"(r5),
-          [m0] "=&v"(m0), [m1] "=&v"(m1), [m2] "=&v"(m2), [m3] "=&v"(m3), [m4] "=&v"(m4), [sT] "=&s"(sT), [sF] "=&s"(sF)
-        : [s0] "v"(s0), [d4] "v"(d4), [mc] "v"(mc), [dlo] "v"(dep_lo), [dhi] "v"(dep_hi), [tb] "v"(tb), [fix] "v"(fix), [mrow] "s"(4u * (uint32_t)RCX_X6_MROW)
-        : "vcc", "scc", "memory");
+          [m4] "=&v"(m4), [sT] "=&s"(sT), [sF] "=&s"(sF)
+        : [s0] "v"(s0), [d4] "v"(d4), [mc] "v"(mc), [dlo] "v"(dep_lo), [dhi] "v"(dep_hi), [tb] "v"(tb), [fix] "v"(fix), [mrow] "s"(4u * (uint32_t)RCX_X6_MROW),
+          [w0] "n"(RCX_R6_NSRC + RCX_R6_NROW - (RCX_X6_PAIR ? 1 : 2)), [w1] "n"(RCX_R6_NSRC + RCX_R6_NROW - 2), [w2] "n"(RCX_R6_NSRC + RCX_R6_NROW - 3),
+          [wm] "n"(RCX_R6_NROW - 1), [wm2] "n"(RCX_X6_PAIR ? 3 : 4),
+          [w0b] "n"(RCX_R6_NSRC + RCX_R6_NROW - 3), [w0c] "n"(RCX_R6_NSRC + RCX_R6_NROW - 4), [w0d] "n"(RCX_R6_NSRC + RCX_R6_NROW - 5), [w0e] "n"(RCX_R6_NSRC + RCX_R6_NROW - 6)
+        : "vcc", "scc", "memory", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53");
     return pend;
 }
 #define RCX_HAVE_ROUNDS6 1
@@ -139,7 +217,7 @@ struct Lz4X6 : Base {
     // 26 cycles of a CU at sixteen waves (43), exact across lanes that share dwords.
     // Anything else -- and whatever emit6 finds at second sight: output that does not fit, an offset beyond the output, a gathered match
     // that starts in the block's first four bytes -- goes through emit5 as before.
-    RCX_LDS_AS uint32_t* mtab = nullptr;                              // LDS: 20 entries of 8 dwords (5 used)
+    RCX_LDS_AS uint32_t* mtab = nullptr;                              // LDS: 20 rows of RCX_X6_MROW dwords (5 used)
 
     __device__ __forceinline__ void mtab_init()
     {
@@ -151,22 +229,28 @@ struct Lz4X6 : Base {
         rcx_wave_sync();
     }
     // bytes [a, a + n) of the frame {w0..w4} to the 4-byte aligned LDS address fp (a < 4, n <= 16); NW: dwords of the frame that can hold any
+    // (NW = 0: five, the fifth skipped -- one scalar compare and branch inside the store -- when no lane is in `any5`)
     template <int NW>
-    __device__ __forceinline__ void store_frame(uint8_t* fp, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, uint32_t a, uint32_t n)
+    __device__ __forceinline__ void store_frame(uint8_t* fp, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, uint32_t a, uint32_t n, unsigned long long any5 = ~0ull)
     {
 #ifdef RCX_NO_MSKOR_ASM
         const uint32_t w[5] = {w0, w1, w2, w3, w4};
-        for (uint32_t j = a; j < a + n; j++) fp[j] = (uint8_t)(w[j >> 2] >> (8u * (j & 3u)));
+        for (uint32_t j = a; j < a + n && j < (NW ? 4u * (uint32_t)NW : any5 ? 20u : 16u); j++) fp[j] = (uint8_t)(w[j >> 2] >> (8u * (j & 3u)));      // (a byte beyond NW dwords is lost here as it is there)
 #else
         const RCX_LDS_AS uint32_t* te = mtab + (uint32_t)RCX_X6_MROW * (a + n);
-#if RCX_X6_MROW == 8
-        const rcx_u32x4 mv = *(const RCX_LDS_AS rcx_u32x4*)te;
+#if RCX_X6_MROW_WIDE
+        const rcx_u32x4 mv = *(const RCX_LDS_AS rcx_u32x4*)te;                          // (16-byte aligned rows: ds_read_b128)
 #else
-        rcx_u32x4 mv; mv[0] = te[0]; mv[1] = te[1]; mv[2] = te[2]; mv[3] = te[3];       // (rows of nine dwords: no two rows' k-th dwords in one bank)
+        rcx_u32x4 mv; mv[0] = te[0]; mv[1] = te[1]; mv[2] = te[2]; mv[3] = te[3];       // (hipcc: two ds_read2_b32)
 #endif
         const uint32_t m0 = mv[0] & (0xffffffffu << (8u * a));
         const uint32_t fa = (uint32_t)(uintptr_t)fp;                 // (low half of a generic LDS pointer = the LDS byte address)
-        if (NW >= 5) {
+        if (NW == 0) {
+            const uint32_t m4 = te[4];
+            asm volatile("ds_mskor_b32 %0, %1, %2\n\tds_mskor_b32 %0, %3, %4 offset:4\n\tds_mskor_b32 %0, %5, %6 offset:8\n\tds_mskor_b32 %0, %7, %8 offset:12\n\t"
+                         "s_cmp_eq_u64 %11, 0\n\ts_cbranch_scc1 L_f4_%=\n\tds_mskor_b32 %0, %9, %10 offset:16\n\tL_f4_%=:"
+                         :: "v"(fa), "v"(m0), "v"(w0 & m0), "v"(mv[1]), "v"(w1 & mv[1]), "v"(mv[2]), "v"(w2 & mv[2]), "v"(mv[3]), "v"(w3 & mv[3]), "v"(m4), "v"(w4 & m4), "s"(any5) : "memory", "scc");
+        } else if (NW >= 5) {
             const uint32_t m4 = te[4];
             asm volatile("ds_mskor_b32 %0, %1, %2\n\tds_mskor_b32 %0, %3, %4 offset:4\n\tds_mskor_b32 %0, %5, %6 offset:8\n\tds_mskor_b32 %0, %7, %8 offset:12\n\tds_mskor_b32 %0, %9, %10 offset:16"
                          :: "v"(fa), "v"(m0), "v"(w0 & m0), "v"(mv[1]), "v"(w1 & mv[1]), "v"(mv[2]), "v"(w2 & mv[2]), "v"(mv[3]), "v"(w3 & mv[3]), "v"(m4), "v"(w4 & m4) : "memory");
@@ -175,6 +259,17 @@ struct Lz4X6 : Base {
                          :: "v"(fa), "v"(m0), "v"(w0 & m0), "v"(mv[1]), "v"(w1 & mv[1]), "v"(mv[2]), "v"(w2 & mv[2]), "v"(mv[3]), "v"(w3 & mv[3]) : "memory");
         }
 #endif
+    }
+
+    // store_frame by the lanes with n != 0, every lane of the wave here (the ballot): four atomics when none of them reaches the fifth dword
+    __device__ __forceinline__ void store_frame_w(uint8_t* fp, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, uint32_t a, uint32_t n)
+    {
+        const unsigned long long any5 = (RCX_X6_NW4 & 2) ? __ballot(n != 0u && a + n > 16u) : ~0ull;
+#ifdef RCX_X6_FRAME_STATS
+        { const bool any = __ballot(n != 0u) != 0, none5 = __ballot(n != 0u && a + n > 16u) == 0;       // (every lane takes part in a ballot)
+          RCX_X6_STAT(0, this->lane == 0 && any); RCX_X6_STAT(1, this->lane == 0 && any && none5); }
+#endif
+        if (n) store_frame<(RCX_X6_NW4 & 2) ? 0 : 5>(fp, w0, w1, w2, w3, w4, a, n, any5);
     }
 
     // One plain batch (ns entries, lane i holds entry i's word; p0: where the batch's first token starts).  Returns false -- nothing
@@ -284,8 +379,8 @@ struct Lz4X6 : Base {
         {
             const uint32_t n1 = L < 16u ? L : 16u;
             uint8_t* fp = wb_ + (li_o - (int32_t)a1);
-            if (n1) store_frame<5>(fp, g0[0], g0[1], g0[2], g0[3], g1[0], a1, n1);
-            if (lit2) { if (L > 16u) store_frame<5>(fp + 16, g1[0], g1[1], g1[2], g1[3], g2, a1, L - n1); }
+            store_frame_w(fp, g0[0], g0[1], g0[2], g0[3], g1[0], a1, n1);
+            if (lit2) store_frame_w(fp + 16, g1[0], g1[1], g1[2], g1[3], g2, a1, L - n1);
         }
 #if RCX_X6_EARLY
         // ---- history-only window matches: the source -- redirection is done -- ends at or below oend0, so its bytes have stood since the previous
@@ -295,7 +390,7 @@ struct Lz4X6 : Base {
         // into what the literal stores are writing -- into the gathered matches' registers, goes out with their store and enters the rounds with
         // nothing to copy: whoever waits for it alone is ready in the first round.
         const bool early = M != 0u && !isfar && !inb && off >= M && (RCX_X6_EARLY == 1 || M <= 16u);
-        RCX_V8_STAT(15, early);
+        RCX_V8_STAT(15, early); RCX_X6_STAT(2, M != 0u && isfar);
         if (early) {
             const int32_t sb = (int32_t)(mdst - S) - lbase - (int32_t)a2;
 #ifdef RCX_NO_MSKOR_ASM
@@ -322,8 +417,8 @@ struct Lz4X6 : Base {
 #endif
             const uint32_t n1 = mf < 16u ? mf : 16u;
             uint8_t* fp = wb_ + (li_m - (int32_t)a2);
-            if (n1) store_frame<5>(fp, f0[0], f0[1], f0[2], f0[3], f1[0], a2, n1);
-            if (mf > 16u) store_frame<5>(fp + 16, f1[0], f1[1], f1[2], f1[3], f2, a2, mf - n1);
+            store_frame_w(fp, f0[0], f0[1], f0[2], f0[3], f1[0], a2, n1);
+            if (__ballot(mf > 16u)) store_frame_w(fp + 16, f1[0], f1[1], f1[2], f1[3], f2, a2, mf - n1);
         }
         rcx_wave_sync();
         X6P_ADD(6);
@@ -389,8 +484,8 @@ struct Lz4X6 : Base {
                 if (nv) { r0 = q[0]; r1 = q[1]; r2 = q[2]; r3 = q[3]; r4 = q[4]; r5 = q[5]; }
                 rcx_wave_sync();
                 // (only the lanes that copy: an LDS atomic under an empty mask still takes its turn at the dwords it shares with its neighbours)
-                if (nv) store_frame<5>(wb_ + (dfr + (int32_t)prog), RCX_ALIGNBYTE(r1, r0, sh), RCX_ALIGNBYTE(r2, r1, sh), RCX_ALIGNBYTE(r3, r2, sh),
-                               RCX_ALIGNBYTE(r4, r3, sh), RCX_ALIGNBYTE(r5, r4, sh), a2, nv);
+                store_frame_w(wb_ + (dfr + (int32_t)prog), RCX_ALIGNBYTE(r1, r0, sh), RCX_ALIGNBYTE(r2, r1, sh), RCX_ALIGNBYTE(r3, r2, sh),
+                              RCX_ALIGNBYTE(r4, r3, sh), RCX_ALIGNBYTE(r5, r4, sh), a2, nv);
                 if (fill) fill_run();                                  // (a ready run's period stands: nobody writes it any more, nobody reads the run yet)
                 rcx_wave_sync();
                 prog += fill ? Mc : nv;
