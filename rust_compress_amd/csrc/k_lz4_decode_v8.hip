@@ -58,6 +58,20 @@
 #ifndef RCX_WALK_STEPS
 #define RCX_WALK_STEPS 16                  /* steps of the ISA walk between two looks at the ring (ring_prio): 4 / 8 / 16 / 64: 0.4604 / 0.4587 / 0.4565 / 0.479 ms */
 #endif
+#ifndef RCX_WALK_READ
+#define RCX_WALK_READ 2                    /* how a step of walk_steps2 reads the token's bytes.  3: three ds_read_b32 at ad & ~3 (32 banks; the lanes start 16 dwords apart, so
+                                            every other lane of a 32-lane group sits on one bank: a 16-way conflict on each read at a chunk's start).  2: two ds_read_b64 at
+                                            ad & ~7 and + 8 (64 banks: half as many lanes collide, and two array accesses instead of three), the step's three dwords chosen by
+                                            bit 2 of ad.  The bank model is benchmarks/lz4_walk_banks.py (71.7 -> 42.4 LDS-array cycles a batch); measured a batch, 3 -> 2:
+                                            SQ_LDS_IDX_ACTIVE 424.5 -> 395.1, SQ_LDS_BANK_CONFLICT 116.8 -> 94.0, LDS instructions 99.5 -> 96.3, vector 544.3 -> 557.8, and
+                                            0.4152 -> 0.4105 ms (docs/LAB_NOTEBOOK.md, "Walk reads") */
+#endif
+#ifndef RCX_HDR_PACK
+#define RCX_HDR_PACK 0                     /* 1: the batch header's usual words (ns, why, plain, p0) as ONE 64-bit store by the parser and one 64-bit read by the executor;
+                                            0: three dword stores, three reads and three scalar moves.  Measured a batch, 0 -> 1: SQ_LDS_IDX_ACTIVE -4.2, LDS instructions
+                                            -2.0, vector -2.0, scalar +3.3 (the packing and unpacking), 0.4152 -> 0.4139 ms alone and 0.4105 -> 0.4099 on top of
+                                            RCX_WALK_READ 2: inside the runs' spread both times, so it stays off (docs/LAB_NOTEBOOK.md, "Walk reads") */
+#endif
 #ifndef RCX_WALK_ISA_LOW
 #define RCX_WALK_ISA_LOW 3
 #endif
@@ -159,7 +173,7 @@ struct Lz4V8 : Lz4X6<Lz4V5<1024, TC, HH, PROF8, SB, false, MIRROR>, PROF8> {
     // The ring between the two waves: EIGHT batches deep -- between the last batch of a chunk and the first of the next the parser
     // stages, walks and links (~55K cycles alone; the executor takes ~10K a batch) -- and a batch entry is ONE word,
     // L | M << 8 | offset << 16: where the literals lie follows from the token's position, and that from the position of the
-    // batch's first token (hdr[7]) and the sizes of the tokens in front (3 + L bytes, + 1 from L = 15 on, + 1 from M = 19 on:
+    // batch's first token (hdr[1] beside the packed ns / why / plain word, RCX_HDR_PACK; hdr[7] without it) and the sizes of the tokens in front (3 + L bytes, + 1 from L = 15 on, + 1 from M = 19 on:
     // up to the per-lane caps each extension is a single byte), a wave scan on the executor's side.
     static constexpr int NSLOT8 = 8;
     struct Slot8 { uint32_t hdr[8]; uint32_t d[64]; };
@@ -328,22 +342,54 @@ struct Lz4V8 : Lz4X6<Lz4V5<1024, TC, HH, PROF8, SB, false, MIRROR>, PROF8> {
     // 12 on the scalar port with branches and waits (hipcc's loop: ~33 + ~45; walk_steps: 30 + 9 and ~22).  `exec` stays narrowed from
     // step to step (a lane past its bound stays there).  Leaves with `slow` = the lanes whose token it does not decide (a run of
     // 255s, an extension byte that is not staged), NOT advanced, or with steps = ~0 when no lane walks any more.
+    //
+    // The step's READS (RCX_WALK_READ).  3: three ds_read_b32 at ad & ~3.  2: two ds_read_b64, at a8 = ad & ~7 and a8 + 8 -- sixteen bytes, of which the step
+    // uses the three dwords from ad & ~3 on: bit 2 of ad, spread over a register (v_bfe_i32), picks them with three v_bfi; + 4 vector instructions a step
+    // (26 + 12), none on the scalar port, one LDS instruction fewer.  (The byte read for an extension beyond the eight bytes stays at "hop > 7": taking it
+    // from the sixteen in hand would cost a second v_perm and a select every step.)  A qword lands in a register PAIR whose halves an asm operand cannot name, so the four data
+    // registers are v[44:47] by name, declared clobbered (as the copy rounds' are, k_lz4_emit6.hip).
+    // Why the sixteen bytes are always staged: cbuf is 16-byte aligned (the kernel's static_assert) and ad >= cbuf, so a8 >= cbuf; a walking lane has
+    // ad < ead <= cbuf + PRE + CH (its segment's end, a chunk's at most), so a8 + 15 <= ad + 15 < cbuf + PRE + CH + 15, inside the CSLACK = 32 bytes that stage8
+    // writes behind every chunk -- whole 16-byte rows, zero-filled where the input has ended, the last chunk's tail included; and ead <= n - 19 as well, so
+    // there ad + 15 <= n - 5: the bytes the step decides on are the block's own, never the zero fill.  (The three dwords reached ad + 11.)
     __device__ __forceinline__ uint64_t walk_steps2(uint32_t& ad, uint32_t ead, uint32_t sgad, uint64_t& m, uint32_t& steps) const
     {
+        static_assert(RCX_WALK_READ == 2 || RCX_WALK_READ == 3, "RCX_WALK_READ: 2 (two aligned qwords) or 3 (three dwords)");
+        static_assert(CSLACK >= 16 && (PRE % 8) == 0, "walk_steps2 reads sixteen bytes from ad & ~7");
         const uint32_t cend = RCX_U((uint32_t)(uintptr_t)this->cbuf + (uint32_t)CBUF8);
-        uint32_t a4, sh, d0, d1, d2, w0, w1, L, t1, hop, tm, x, rel, t2;
+#if RCX_WALK_READ == 3
+        uint32_t d0, d1, d2;
+#define RCX_W2_D0 "%[d0]"
+#define RCX_W2_D1 "%[d1]"
+#define RCX_W2_D2 "%[d2]"
+#else
+#define RCX_W2_D0 "v44"
+#define RCX_W2_D1 "v45"
+#define RCX_W2_D2 "v46"
+#define RCX_W2_D3 "v47"
+#endif
+        uint32_t a4, sh, w0, w1, L, t1, hop, tm, x, rel, t2;
         uint64_t slow = 0, sA, sB, sW, bit;
         asm volatile(
             "L_top_%=:\n\t"
             "v_cmp_lt_u32_e32 vcc, %[ad], %[ead]\n\t"
             "s_cbranch_vccz L_none_%=\n\t"
             "s_mov_b64 exec, vcc\n\t"
+#if RCX_WALK_READ == 3
             "v_and_b32_e32 %[a4], -4, %[ad]\n\t"
             "ds_read_b32 %[d0], %[a4]\n\t"
             "ds_read_b32 %[d1], %[a4] offset:4\n\t"
             "ds_read_b32 %[d2], %[a4] offset:8\n\t"
             "v_sub_u32_e32 %[rel], %[ad], %[sgad]\n\t"                  // the mark, while the bytes are on their way
             "v_and_b32_e32 %[sh], 3, %[ad]\n\t"
+#else
+            "v_and_b32_e32 %[a4], -8, %[ad]\n\t"
+            "ds_read_b64 v[44:45], %[a4]\n\t"
+            "ds_read_b64 v[46:47], %[a4] offset:8\n\t"
+            "v_sub_u32_e32 %[rel], %[ad], %[sgad]\n\t"                  // the mark, while the bytes are on their way
+            "v_and_b32_e32 %[sh], 3, %[ad]\n\t"
+            "v_bfe_i32 %[t1], %[ad], 2, 1\n\t"                          // all ones where the token lies in the qword's upper half
+#endif
             "v_cmp_gt_u32_e32 vcc, 64, %[rel]\n\t"                     // (two steps in three are head start: no lane in its own segment yet)
             "s_cbranch_vccz L_nomark_%=\n\t"
             "s_and_saveexec_b64 %[sW], vcc\n\t"
@@ -352,8 +398,13 @@ struct Lz4V8 : Lz4X6<Lz4V5<1024, TC, HH, PROF8, SB, false, MIRROR>, PROF8> {
             "s_mov_b64 exec, %[sW]\n\t"
             "L_nomark_%=:\n\t"
             "s_waitcnt lgkmcnt(0)\n\t"
-            "v_alignbyte_b32 %[w0], %[d1], %[d0], %[sh]\n\t"
-            "v_alignbyte_b32 %[w1], %[d2], %[d1], %[sh]\n\t"
+#if RCX_WALK_READ == 2
+            "v_bfi_b32 " RCX_W2_D0 ", %[t1], " RCX_W2_D1 ", " RCX_W2_D0 "\n\t"      // the three dwords from ad & ~3 on, in place
+            "v_bfi_b32 " RCX_W2_D1 ", %[t1], " RCX_W2_D2 ", " RCX_W2_D1 "\n\t"
+            "v_bfi_b32 " RCX_W2_D2 ", %[t1], " RCX_W2_D3 ", " RCX_W2_D2 "\n\t"
+#endif
+            "v_alignbyte_b32 %[w0], " RCX_W2_D1 ", " RCX_W2_D0 ", %[sh]\n\t"
+            "v_alignbyte_b32 %[w1], " RCX_W2_D2 ", " RCX_W2_D1 ", %[sh]\n\t"
             "v_bfe_u32 %[L], %[w0], 4, 4\n\t"
             "v_bfe_u32 %[t1], %[w0], 8, 8\n\t"
             "v_cmp_eq_u32_e32 vcc, 15, %[L]\n\t"
@@ -398,10 +449,22 @@ struct Lz4V8 : Lz4X6<Lz4V5<1024, TC, HH, PROF8, SB, false, MIRROR>, PROF8> {
             "L_out_%=:\n\t"
             "s_mov_b64 exec, -1\n\t"
             : [ad] "+v"(ad), [m] "+v"(m), [steps] "+s"(steps), [slow] "+s"(slow), [sA] "=&s"(sA), [sB] "=&s"(sB), [sW] "=&s"(sW),
+#if RCX_WALK_READ == 3
               [a4] "=&v"(a4), [sh] "=&v"(sh), [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [w0] "=&v"(w0), [w1] "=&v"(w1), [L] "=&v"(L),
+#else
+              [a4] "=&v"(a4), [sh] "=&v"(sh), [w0] "=&v"(w0), [w1] "=&v"(w1), [L] "=&v"(L),
+#endif
               [t1] "=&v"(t1), [hop] "=&v"(hop), [tm] "=&v"(tm), [x] "=&v"(x), [rel] "=&v"(rel), [bit] "=&v"(bit), [t2] "=&v"(t2)
             : [ead] "v"(ead), [sgad] "v"(sgad), [cend] "s"(cend), [k274] "s"(274u), [ksel] "s"(0x0c0c0000u)
+#if RCX_WALK_READ == 3
             : "vcc", "scc", "memory");
+#else
+            : "vcc", "scc", "memory", "v44", "v45", "v46", "v47");
+#endif
+#undef RCX_W2_D0
+#undef RCX_W2_D1
+#undef RCX_W2_D2
+#undef RCX_W2_D3
         return slow;
     }
 #endif
@@ -768,7 +831,13 @@ struct Lz4V8 : Lz4X6<Lz4V5<1024, TC, HH, PROF8, SB, false, MIRROR>, PROF8> {
             if (why == B::SOLO_ || why == B::WIDE_) { const uint32_t r = po > (uint32_t)B::RH ? po - (uint32_t)B::RH : 0u; prlo = r > prlo ? r : prlo; }
         }
         if (lane == 0) {
+#if RCX_HDR_PACK
+            // (ns <= 64, why < 256: one word; with p0 beside it the usual header is ONE ds_write_b64 -- a store costs its register transfer,
+            // not its lanes -- and one 64-bit read and two scalar moves on the executor's side.  A slot is 288 bytes: hdr[0] is 8-byte aligned)
+            *(RCX_LDS_AS uint64_t*)&sl->hdr[0] = (uint64_t)((uint32_t)ns | ((uint32_t)why << 8) | (plain ? 0x10000u : 0u)) | ((uint64_t)p0 << 32);
+#else
             sl->hdr[0] = (uint32_t)ns; sl->hdr[1] = (uint32_t)why | (plain ? 0x100u : 0u); sl->hdr[7] = p0;
+#endif
             if (why != B::GO) {                                      // (the executor reads these behind a batch with a reason only)
                 sl->hdr[2] = (uint32_t)perr; sl->hdr[3] = gL; sl->hdr[4] = gM; sl->hdr[5] = goff; sl->hdr[6] = gsrc;
             }
@@ -873,10 +942,18 @@ struct Lz4V8 : Lz4X6<Lz4V5<1024, TC, HH, PROF8, SB, false, MIRROR>, PROF8> {
             rcx_wave_sync();
             const RCX_LDS_AS Slot8* sl = &ring->slot[tail % NSLOT8];
             typename B::Batch bt;
+#if RCX_HDR_PACK
+            const uint64_t h01_ = *(const RCX_LDS_AS uint64_t*)&sl->hdr[0];           // ns | why << 8 | plain << 16, p0: one read, two scalar moves
+            uint32_t w1 = sl->d[lane];
+            const uint32_t hw_ = RCX_U((uint32_t)h01_), h7_ = (uint32_t)(h01_ >> 32);
+            bt.ns = (int)(hw_ & 0xffu); bt.why = (int)((hw_ >> 8) & 0xffu);
+            const bool plain6 = X6 && RCX_X6_MODE != 2 && (hw_ & 0x10000u) != 0u;
+#else
             const uint32_t h0_ = sl->hdr[0], h1_ = sl->hdr[1], h7_ = sl->hdr[7];      // (all of the slot's usual reads in one LDS round trip)
             uint32_t w1 = sl->d[lane];
             bt.ns = (int)RCX_U(h0_); bt.why = (int)(RCX_U(h1_) & 0xffu);
             const bool plain6 = X6 && RCX_X6_MODE != 2 && (RCX_U(h1_) & 0x100u) != 0u;
+#endif
             {   // (looked at only behind a batch with a reason: left undefined -- five s_mov a batch on the executor's chain)
                 uint32_t u_;
                 RCX_NOINIT_S(u_);
@@ -1221,6 +1298,9 @@ __global__ __launch_bounds__(128, 8) void k_lz4_decode_v8(rcx_kargs a, int only_
     __shared__ __align__(16) uint8_t s_wbuf[S::WBUF5 + 16 + (X6 ? 16 : 0)];    // (X6: 16 bytes in front -- a source frame starts up to 3 bytes below the window)
     __shared__ __align__(16) typename S::Ring8 s_ring;
     __shared__ __align__(16) uint8_t s_cbuf[S::CBUF8 + 16];
+#if !defined(RCX_NO_WALK_ASM)             /* (the simulator's build has neither the attribute nor the hand-written walk) */
+    static_assert(__alignof__(s_cbuf) >= 16, "stage8 stores 16 bytes a lane, and walk_steps2 reads aligned qwords from (address & ~7) on: that must not fall below the buffer");
+#endif
     __shared__ int16_t s_list[S::LISTN];
     __shared__ uint32_t s_lmap[64];
     // sixteen workgroups a CU (eight waves a SIMD) need <= 10240 bytes each: the shipped instantiation stands at 10192 with rows of twelve dwords
